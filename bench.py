@@ -15,6 +15,12 @@ DataFrames, so the timed region includes host->device ingest, every kernel, ever
 collective and model construction. ``value`` = geometric-mean speedup of our fit time over
 the Spark-ML CPU fit time; ``vs_baseline`` = value / the reference GPU's own
 geometric-mean speedup on the same table (20.1x).
+
+A plain run sets up, warms up, times the K steps and prints the result line. ``--full`` adds, per
+workload and outside the timed steps, one timed transform pass and the held-out quality metrics
+(``transform_s`` / ``quality`` in the result line). ``--dump-outputs DIR`` writes what the last
+timed fit of each workload returned (the model's arrays) as ``DIR/<workload>.<attribute>.npy``;
+the data are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -45,6 +51,49 @@ def _batched_frame(X, y, batch_rows):
     return DataFrame([pa.Table.from_batches(rbs)])
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay under this
+DUMP_ARRAY_ELEMS = 1 << 20  # a larger attribute is written as a fixed seeded sample of this many elements
+DUMP_SKIP = ("phase_s",)  # wall-clock attributes: not a result of the computation
+
+
+def _dump_outputs(out_dir: str, name: str, model, budget: int) -> int:
+    """Write every numeric attribute of a fitted model (what ``fit`` hands its caller: centres,
+    components, coefficients, packed trees, iteration counts) as ``out_dir/<name>.<attribute>.npy``,
+    float32 for float32 / float16 values and float64 for everything else (integers exactly). Returns
+    the bytes written; never more than ``budget``."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    attrs = dict(model._get_model_attributes())
+    for key, v in list(attrs.items()):
+        if isinstance(v, list) and v and all(isinstance(t, dict) for t in v):
+            # a forest: one dict of flat node arrays per tree -> per field, all trees' nodes in tree order
+            del attrs[key]
+            for sub in sorted(v[0]):
+                attrs["%s.%s" % (key, sub)] = np.concatenate([np.asarray(t[sub]).reshape(-1) for t in v])
+    written = 0
+    for key in sorted(attrs):
+        if key in DUMP_SKIP or attrs[key] is None:
+            continue
+        try:
+            a = np.asarray(attrs[key])
+        except ValueError:  # ragged nested lists
+            continue
+        if a.dtype.kind not in "biuf":  # strings, JSON blobs, objects
+            continue
+        a = a.astype(np.float32 if a.dtype in (np.float32, np.float16) else np.float64)
+        cap = min(DUMP_ARRAY_ELEMS, (budget - written) // a.itemsize - 64)  # 64 elements: the .npy header
+        if cap <= 0:
+            break
+        if a.size > cap:  # the same elements in every run: seeded by the element count alone
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        path = os.path.join(out_dir, "%s.%s.npy" % (name, key))
+        np.save(path, a, allow_pickle=False)
+        written += os.path.getsize(path)
+    return written
+
+
 def _spawn_ranks(n: int) -> int:
     """Re-run this command as an n-rank torch.distributed job on this node (127.0.0.1 rendezvous)."""
     import socket
@@ -73,16 +122,26 @@ def main() -> None:
                     help="pinned: each rank's shard is one page-locked buffer (headline); batches: pageable "
                          "Arrow record batches of --batch-rows rows, as Spark's mapInArrow delivers them")
     ap.add_argument("--batch-rows", type=int, default=20000)
+    ap.add_argument("--full", action="store_true",
+                    help="after each workload's timed fits also time one transform pass and score the model on "
+                         "held-out rows (transform_s / quality per workload); a plain run only fits")
     ap.add_argument("--no-transform", action="store_true",
-                    help="skip the per-workload transform timing (outside the timed fit steps)")
+                    help="with --full: skip the per-workload transform timing (outside the timed fit steps)")
     ap.add_argument("--no-quality", action="store_true",
-                    help="skip the held-out quality metrics (scored after the timed fits)")
+                    help="with --full: skip the held-out quality metrics (scored after the timed fits)")
     ap.add_argument("--dump-models", type=str, default=None,
                     help="saves each workload's last fitted model under this directory (rank 0 writes)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the numeric attributes of each workload's last fitted model "
+                         "as DIR/<workload>.<attribute>.npy (float32 / float64, at most 64 MB in all; rank 0 writes)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: start the N ranks ourselves (one process per GPU) from this parent,
         # which has not touched the GPU, and exit with the launcher's status
@@ -155,6 +214,7 @@ def main() -> None:
 
     results = {}
     errors = {}
+    dumped = 0  # bytes written under --dump-outputs so far
     for name in names:
         wl = reg.get(name)
         if wl is None:
@@ -205,7 +265,7 @@ def main() -> None:
                 "evidence": model_evidence(name, model),
                 "per_rank": per_rank,
             }
-            if not args.no_transform:
+            if args.full and not args.no_transform:
                 # reference BenchmarkBase times transform separately (benchmark/base.py:221-271):
                 # one pass of model.transform over this rank's rows (H2D + kernels + D2H of the
                 # output columns), outside the fit steps; failures are recorded, never fatal
@@ -225,7 +285,7 @@ def main() -> None:
                     del out
                 except Exception as e:  # noqa: BLE001
                     results[name]["transform_error"] = repr(e)[:200]
-            if rank == 0 and not args.no_quality:
+            if rank == 0 and args.full and not args.no_quality:
                 # held-out quality next to the speed (outside every timed region): fresh rows of the
                 # same family and ground truth, scored through the public transform API
                 H = min(HOLDOUT_ROWS, max(1, m_local))
@@ -234,6 +294,8 @@ def main() -> None:
                 del Xq, yq
             if args.dump_models:  # every rank calls save; under SPMD rank 0 alone writes
                 model.write().overwrite().save(os.path.join(args.dump_models, name))
+            if args.dump_outputs and rank == 0:
+                dumped += _dump_outputs(args.dump_outputs, name, model, DUMP_BYTES - dumped)
             del df, Xh, yh, model
         except Exception as e:  # noqa: BLE001
             errors[name] = repr(e)[:400]

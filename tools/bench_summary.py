@@ -1,5 +1,6 @@
-"""One line per workload of a bench.py JSON output file: fit seconds, evidence, quality, and the
-step summary. python tools/bench_summary.py <bench-output-file>"""
+"""One line per workload of a bench.py JSON output file: fit seconds, evidence, and the step
+summary; transform seconds and quality where the run was made with ``bench.py --full`` (None
+otherwise). python tools/bench_summary.py <bench-output-file>"""
 import json
 import sys
 

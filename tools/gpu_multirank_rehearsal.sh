@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out
 for n in ${NS:-2 4}; do
   SRML_DIST_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 1 --warmup 1 \
+    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 1 --warmup 1 --full \
     > gpurun_out/rehearsal_$n.json 2> gpurun_out/rehearsal_$n.err || { echo "n=$n failed"; tail -30 gpurun_out/rehearsal_$n.err; exit 1; }
   python - "$n" <<'PY'
 import json, sys
