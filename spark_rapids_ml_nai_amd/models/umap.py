@@ -15,6 +15,9 @@ Semantics follow umap-learn / cuML UMAP (what the reference calls on one GPU, ``
   split-K fp64 GEMMs (larger n); host ``eigsh`` only on CPU; scaled like umap-learn;
 * SGD: ``srml_umap_epoch`` (edge-parallel HIP kernel, hash RNG negative sampling), alpha decays
   linearly, edges below max_w / n_epochs dropped, epochs_per_sample = n_epochs / (n_epochs·w/max_w);
+  in deterministic mode (``utils.determinism``) synchronous epochs instead (``srml_umap_epoch_sync``:
+  every edge reads the epoch's starting layout, moves summed in edge order), so a seeded fit or
+  transform repeats bit for bit;
 * transform: kNN to the training data, local_connectivity - 1, l1-normalised weighted init
   from neighbour embeddings, n_epochs/3 (default 100 / 30) epochs at alpha/4 with the training
   embedding fixed.
@@ -29,6 +32,8 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..utils.determinism import deterministic
+from ..utils.log import get_logger
 
 SMOOTH_K_TOLERANCE = 1e-5
 MIN_K_DIST_SCALE = 1e-3
@@ -384,7 +389,17 @@ def _spectral_dense_device(rows: torch.Tensor, cols: torch.Tensor, vals: torch.T
     Jacobi kernel (``ops.syevj``); the top non-trivial eigenvectors of M are the smallest
     non-trivial ones of the normalised Laplacian (umap-learn's spectral_layout)."""
     dev = vals.device
-    deg = ops.zeros(n, dtype=torch.float64, device=dev).index_add_(0, rows.long(), vals.double())
+    r64 = rows.long()
+    if deterministic() and dev.type == "cuda" and (r64.numel() < 2 or bool((r64[1:] >= r64[:-1]).all())):
+        # index_add_ on the device is fp64 atomics in arrival order: the row sums of the row-sorted
+        # edges as a CSR instead (one row group per row, fixed order)
+        from ..core.base import CSR
+
+        indptr = torch.searchsorted(r64.contiguous(), torch.arange(n + 1, device=dev, dtype=torch.int64))
+        deg = ops.csr_row_sums(CSR(indptr=indptr, indices=cols.to(torch.int32).contiguous(),
+                                   data=vals.float().contiguous(), shape=(n, n)))
+    else:
+        deg = ops.zeros(n, dtype=torch.float64, device=dev).index_add_(0, r64, vals.double())
     dinv = 1.0 / torch.sqrt(deg.clamp_min(1e-30))
     M = ops.zeros((n, n), dtype=torch.float64, device=dev)
     M.index_put_((rows.long(), cols.long()), dinv[rows.long()] * vals.double() * dinv[cols.long()], accumulate=True)
@@ -427,7 +442,17 @@ def optimize_layout(emb_head: torch.Tensor, emb_tail: torch.Tensor, head: torch.
     replicas are re-synchronised by ONE all-reduce of the layout deltas per epoch (N x dim fp32;
     160 MB at the 20M-row north-star — a few hundred microseconds over the xGMI mesh). The
     summed deltas are the union of every rank's Hogwild updates, as on one device.
+
+    Deterministic mode (``utils.determinism``): synchronous epochs (``ops.umap_epoch_sync``).
+    Every edge reads the layout of the epoch's start and the moves of a vertex are summed in
+    edge order, so the layout is a pure function of (graph, initial layout, seed). Only heads
+    move, so a fit (``move_other``) always takes the pull form: its graph, the fuzzy union and
+    the categorical intersection after it, has a symmetric pattern. On several ranks the ranks'
+    summed moves ``D`` are all-reduced and added.
     """
+    det = deterministic()
+    if det and move_other:
+        pull = True
     w = torch.where(w < w.max() / float(n_epochs), torch.zeros_like(w), w)
     keep = w > 0
     head, tail, w = head[keep], tail[keep], w[keep]
@@ -451,8 +476,24 @@ def optimize_layout(emb_head: torch.Tensor, emb_tail: torch.Tensor, head: torch.
         g = torch.Generator(device=emb_tail.device).manual_seed(int(seed) + 7)
         ids = torch.randperm(nt, generator=g, device=emb_tail.device)[: (nt // 8) * 8].int().contiguous()
         neg = (torch.empty((ids.shape[0], emb_tail.shape[1]), dtype=torch.float32, device=emb_tail.device), ids)
+    indptr = ws = None
+    if det and emb_head.is_cuda:  # once per fit: the CSR row pointer of the head-sorted edges
+        nh = emb_head.shape[0]
+        indptr = torch.searchsorted(head.long(), torch.arange(nh + 1, device=head.device, dtype=torch.int64))
+        ws = torch.empty(ops.umap_epoch_sync_ws(head.shape[0], nh, emb_head.shape[1]), dtype=torch.float32,
+                         device=emb_head.device)
     for n in range(n_epochs):
         alpha = initial_alpha * (1.0 - float(n) / float(n_epochs))
+        if det:
+            if neg is not None:
+                ops.umap_neg_table(emb_tail, neg[1], neg[0])
+            D = ops.umap_epoch_sync(head, tail, eps, next_sample, next_neg, eps_neg, emb_head, emb_tail, a, b, gamma,
+                                    alpha, n, move_other, seed, pull=pull, neg_table=neg, indptr=indptr, ws=ws,
+                                    apply=world == 1)
+            if world > 1:
+                ctx.comm.allreduce(D)
+                emb_head.add_(D)
+            continue
         before = (emb_head.clone(), None if same or not move_other else emb_tail.clone()) if world > 1 else None
         if neg is not None:
             ops.umap_neg_table(emb_tail, neg[1], neg[0])
@@ -494,6 +535,9 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
     dim = int(params.get("n_components", 2))
     metric = params.get("metric", "euclidean")
     seed = params.get("random_state")
+    if seed is None and deterministic():
+        get_logger("UMAP").warning("deterministic mode with random_state=None: the fit draws its own seed and "
+                                   "cannot be repeated; set random_state")
     seed = int(seed) if seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
     dist_ctx = ctx if (ctx is not None and ctx.world_size > 1) else None
     if dist_ctx is not None:

@@ -2528,6 +2528,111 @@ def umap_neg_table(emb: torch.Tensor, ids: torch.Tensor, out: torch.Tensor) -> t
     return out
 
 
+_U32 = 0xFFFFFFFF
+
+
+def umap_hash3(a: Any, b: Any, c: Any) -> Any:
+    """``hash3`` of umap.hip on int64 tensors (or Python ints) holding 32-bit words. An int64
+    product of two 32-bit words wraps modulo 2^64, which leaves its low 32 bits intact; every
+    shift acts on a value already masked to 32 bits."""
+    h = ((a * 0x9E3779B1) ^ (((b + 0x7F4A7C15) & _U32) * 0x85EBCA77) ^ (((c + 0x165667B1) & _U32) * 0xC2B2AE3D)) & _U32
+    h = h ^ (h >> 16)
+    h = (h * 0x7FEB352D) & _U32
+    h = h ^ (h >> 15)
+    h = (h * 0x846CA68B) & _U32
+    return h ^ (h >> 16)
+
+
+def umap_neg_draw(seed: int, e: Any, epoch: int, p: Any, n: int, lines: bool = False) -> Any:
+    """Row drawn by edge ``e`` (int64 tensor or int) for its ``p``-th negative sample of ``epoch``,
+    as the epoch kernels draw it: uniform in [0, n) (high half of hash * n), or with ``lines`` a
+    position in the 8 n-row negative table (``n`` random lines; the edges e & ~7 .. e | 7 share one)."""
+    seed, epoch = int(seed) & _U32, int(epoch) & _U32
+    if lines:
+        h = umap_hash3(seed ^ ((e >> 3) & _U32), epoch, (p + 0x2545F491) & _U32)
+        return ((h * int(n)) >> 32) * 8 + (e & 7)
+    h = umap_hash3(seed ^ (e & _U32), epoch, (p + 0x51ED27 * ((e >> 32) & _U32)) & _U32)
+    return (h * int(n)) >> 32  # h < 2^32 and n < 2^31: the product fits in 63 bits
+
+
+def umap_epoch_sync(head: torch.Tensor, tail: torch.Tensor, eps: torch.Tensor, next_sample: torch.Tensor,
+                    next_neg: torch.Tensor, eps_neg: torch.Tensor, emb_head: torch.Tensor, emb_tail: torch.Tensor,
+                    a: float, b: float, gamma: float, alpha: float, epoch: int, move_other: bool, seed: int,
+                    pull: bool = False, neg_table: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                    indptr: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                    apply: bool = True) -> torch.Tensor:
+    """Synchronous epoch ``epoch`` over head-sorted edges: every due edge computes its head's move
+    (attraction, then its negatives one after another, the arithmetic and draws of ``umap_epoch``)
+    from the layout as it stands at the call, the moves of a vertex are summed in edge order and
+    returned as ``D`` [n_head, dim]; ``apply`` also advances the layout, ``emb_head += D``. Only
+    heads move: ``pull`` (symmetric edge lists) or ``move_other=False``. Unlike ``umap_epoch``
+    the result is a pure function of the inputs — bit-reproducible on the device, and equal to
+    the CPU branch below up to the rounding of the hardware log2 / exp2.
+
+    Device only: ``indptr`` is the int64 CSR row pointer of ``head`` (n_head + 1; built here when
+    None) and ``ws`` a float32 workspace of ``umap_epoch_sync_ws`` elements; ``D`` is a view of it."""
+    if move_other and not pull:
+        raise ValueError("umap_epoch_sync moves heads only: pull=True or move_other=False")
+    n_head, dim = emb_head.shape
+    n_tail = emb_tail.shape[0]
+    if emb_head.is_cuda:
+        if indptr is None:
+            indptr = torch.searchsorted(head.long(), torch.arange(n_head + 1, device=head.device, dtype=torch.int64))
+        need = umap_epoch_sync_ws(head.shape[0], n_head, dim)
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.float32, device=emb_head.device)
+        if ws.dtype != torch.float32 or ws.numel() < need or indptr.dtype != torch.int64 \
+                or indptr.numel() != n_head + 1:
+            raise ValueError("umap_epoch_sync: workspace or indptr of the wrong size / dtype")
+        native.call("srml_umap_epoch_sync", head.data_ptr(), tail.data_ptr(), head.shape[0], indptr.data_ptr(),
+                    eps.data_ptr(), next_sample.data_ptr(), next_neg.data_ptr(), eps_neg.data_ptr(),
+                    emb_head.data_ptr(), emb_tail.data_ptr(), n_head, n_tail, dim, float(a), float(b), float(gamma),
+                    float(alpha), float(epoch), int(bool(move_other)), int(bool(pull)), int(seed) & _U32,
+                    neg_table[0].data_ptr() if neg_table is not None else None,
+                    neg_table[1].data_ptr() if neg_table is not None else None,
+                    int(neg_table[0].shape[0] // 8) if neg_table is not None else 0, ws.data_ptr(),
+                    int(bool(apply)), native.stream(emb_head.device))
+        return ws[: n_head * dim].view(n_head, dim)
+    # CPU reference of the same semantics, with the device's counter-based draws
+    ep = float(epoch)
+    D = torch.zeros_like(emb_head)
+    idx = torch.nonzero((eps > 0) & (next_sample <= ep)).view(-1)
+    if idx.numel() == 0:
+        return D
+    j, k = head[idx].long(), tail[idx].long()
+    orig = emb_head[j]
+    diff = orig - emb_tail[k]
+    d2 = (diff * diff).sum(1, keepdim=True)
+    pb = d2.clamp_min(1e-30) ** b
+    coef = torch.where(d2 > 0, (-2.0 * a * b * pb) / (d2.clamp_min(1e-30) * (a * pb + 1.0)), torch.zeros_like(d2))
+    cur = orig + (coef * diff).clamp(-4, 4) * (2.0 * alpha if pull else alpha)
+    next_sample[idx] += eps[idx]
+    en = eps_neg[idx]
+    # truncating, as the kernel's (int) cast
+    n_neg = torch.where(en > 0, torch.trunc((ep - next_neg[idx]) / en.clamp_min(1e-30)), torch.zeros_like(en)).long()
+    table, ids = (emb_tail, None) if neg_table is None else (neg_table[0], neg_table[1].long())
+    for p in range(int(n_neg.max().clamp_min(0))):
+        pos = umap_neg_draw(seed, idx, epoch, p, table.shape[0] // 8 if ids is not None else n_tail, ids is not None)
+        dn = cur - table[pos]
+        d2n = (dn * dn).sum(1, keepdim=True)
+        c = torch.where(d2n > 0, (2.0 * gamma * b) / ((0.001 + d2n) * (a * d2n.clamp_min(1e-30) ** b + 1.0)),
+                        torch.zeros_like(d2n))
+        gn = torch.where(c > 0, (c * dn).clamp(-4, 4), torch.full_like(dn, 4.0))
+        same = (d2n <= 0) & (j == (pos if ids is None else ids[pos])).view(-1, 1)
+        cur = torch.where((p < n_neg).view(-1, 1) & ~same, cur + gn * alpha, cur)
+    next_neg[idx] += n_neg.float() * en
+    D.index_add_(0, j, cur - orig)
+    if apply:
+        emb_head += D
+    return D
+
+
+def umap_epoch_sync_ws(n_edges: int, n_head: int, dim: int) -> int:
+    """float32 elements of ``umap_epoch_sync``'s device workspace: D [n_head][dim] plus two
+    [dim] partial-sum slots per 64-edge wave."""
+    return int(n_head) * int(dim) + 2 * ((int(n_edges) + 63) // 64) * int(dim)
+
+
 # ------------------------------------------------------------------------------------------
 # Symmetric eigensolver (parallel Jacobi, fp64)
 # ------------------------------------------------------------------------------------------

@@ -210,6 +210,181 @@ __global__ __launch_bounds__(256) void umap_epoch_kernel(
   }
 }
 
+// Synchronous ("Jacobi") epoch, the reproducible counterpart of umap_epoch_kernel for head-only
+// moves (pull, or a fixed tail table): every edge reads the layout as it stood at the start of
+// the epoch and nothing this launch reads is written by it, so the epoch is a pure function of
+// (layout, graph, schedule state, seed, epoch) whatever the order the waves run in. The per-edge
+// arithmetic is umap_epoch_kernel's, line for line. The head deltas of a run of equal heads are
+// summed by the same in-wave segmented scan; a run inside one wave stores its sum to delta[j], a
+// run that crosses a wave boundary stores each wave's partial to that wave's own slot
+// part[wave][side] (side 1: the run leaves through lane 63 — its first wave; side 0: it entered
+// through lane 0), and umap_sync_fold_kernel adds the slots in ascending wave order. delta and
+// part are zeroed before the launch, so a wave that takes the idle exit contributes zeros.
+template <int D>
+__global__ __launch_bounds__(256) void umap_epoch_sync_kernel(
+    const int* __restrict__ head, const int* __restrict__ tail, long n_edges, const float* __restrict__ eps,
+    float* __restrict__ next_sample, float* __restrict__ next_neg, const float* __restrict__ eps_neg,
+    const float* __restrict__ emb_head, const float* __restrict__ emb_tail, int n_tail_vertices, int dim, float a,
+    float b, float gamma, float alpha, float epoch, int pull, unsigned seed, const float* __restrict__ neg_tab,
+    const int* __restrict__ neg_ids, int neg_lines, float* __restrict__ delta, float* __restrict__ part) {
+  constexpr int DM = D > 0 ? D : 32;
+  const int lane = threadIdx.x & 63;
+  // the remap only changes which XCD sweeps which edge range; slots are indexed by e, not by block
+  const long e = (long)xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
+  const bool in = e < n_edges;
+  const float eps_e = in ? eps[e] : 0.f;
+  const bool act = eps_e > 0.f && next_sample[e] <= epoch;  // eps_e > 0 implies e < n_edges
+  if (__ballot(act) == 0ull) return;
+  const int dd = D > 0 ? D : dim;
+  const int j = in ? head[e] : -1;
+  const float* hj = emb_head + (long)(j < 0 ? 0 : j) * dd;
+  float cur[DM], orig[DM];
+#pragma unroll
+  for (int d = 0; d < DM; ++d) cur[d] = orig[d] = 0.f;
+  if (act) {
+    const int k = tail[e];
+    const float* tk = emb_tail + (long)k * dd;
+    float dist2 = 0.f;
+#pragma unroll
+    for (int d = 0; d < DM; ++d) {
+      if (d < dd) {
+        cur[d] = hj[d];
+        orig[d] = cur[d];
+        const float diff = cur[d] - tk[d];
+        dist2 = fmaf(diff, diff, dist2);
+      }
+    }
+    float coef = 0.f;
+    if (dist2 > 0.f) {
+      const float pb = fast_pow(dist2, b);
+      coef = __fdividef(-2.f * a * b * pb, dist2 * (a * pb + 1.f));
+    }
+    const float ascale = pull ? 2.f * alpha : alpha;
+#pragma unroll
+    for (int d = 0; d < DM; ++d) {
+      if (d < dd) {
+        const float g = clip4(coef * (cur[d] - tk[d]));
+        cur[d] += g * ascale;
+      }
+    }
+    next_sample[e] += eps_e;
+    const float en = eps_neg[e];
+    const int n_neg = en > 0.f ? (int)((epoch - next_neg[e]) / en) : 0;
+    constexpr int NPF = (D > 0 && D <= 4) ? 8 : 1;
+    for (int p0 = 0; p0 < n_neg; p0 += NPF) {
+      float tnv[NPF][DM];
+      int kkv[NPF];
+#pragma unroll
+      for (int q = 0; q < NPF; ++q) {
+        const int p = p0 + q;
+        kkv[q] = -1;
+        if (p < n_neg) {
+          const float* tn;
+          if (neg_tab != nullptr) {
+            const unsigned h = hash3(seed ^ (unsigned)(e >> 3), (unsigned)epoch, (unsigned)p + 0x2545F491u);
+            const long pos = (long)(((unsigned long long)h * (unsigned)neg_lines) >> 32) * 8 + (e & 7);
+            tn = neg_tab + pos * dd;
+            kkv[q] = (int)pos;
+          } else {
+            const unsigned h =
+                hash3(seed ^ (unsigned)e, (unsigned)epoch, (unsigned)p + 0x51ED27u * (unsigned)(e >> 32));
+            kkv[q] = (int)(((unsigned long long)h * (unsigned)n_tail_vertices) >> 32);
+            tn = emb_tail + (long)kkv[q] * dd;
+          }
+#pragma unroll
+          for (int d = 0; d < DM; ++d)
+            if (d < dd) tnv[q][d] = tn[d];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < NPF; ++q) {
+        if (p0 + q >= n_neg) break;
+        float d2 = 0.f;
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+          if (d < dd) {
+            const float diff = cur[d] - tnv[q][d];
+            d2 = fmaf(diff, diff, d2);
+          }
+        }
+        float c = 0.f;
+        if (d2 > 0.f) {
+          c = __fdividef(2.f * gamma * b, (0.001f + d2) * (a * fast_pow(d2, b) + 1.f));
+        } else if (j == (neg_tab != nullptr ? neg_ids[kkv[q]] : kkv[q])) {
+          continue;
+        }
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+          if (d < dd) {
+            const float g = c > 0.f ? clip4(c * (cur[d] - tnv[q][d])) : 4.f;
+            cur[d] += g * alpha;
+          }
+        }
+      }
+    }
+    next_neg[e] += (float)n_neg * en;
+  }
+  float dl[DM];
+#pragma unroll
+  for (int d = 0; d < DM; ++d) dl[d] = cur[d] - orig[d];
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int jo = __shfl_down(j, o);
+    const bool take = lane + o < 64 && jo == j;
+#pragma unroll
+    for (int d = 0; d < DM; ++d) {
+      if (d < dd) {
+        const float v = __shfl_down(dl[d], o);
+        if (take) dl[d] += v;
+      }
+    }
+  }
+  const int jprev = __shfl_up(j, 1);
+  const bool leader = j >= 0 && (lane == 0 || jprev != j);
+  int jp = -2, jn = -2;
+  if (lane == 0 && e > 0 && e - 1 < n_edges) jp = head[e - 1];
+  if (lane == 63 && e + 1 < n_edges) jn = head[e + 1];
+  jp = __shfl(jp, 0);
+  jn = __shfl(jn, 63);
+  const int j63 = __shfl(j, 63);
+  if (!leader) return;
+  bool nz = false;
+#pragma unroll
+  for (int d = 0; d < DM; ++d)
+    if (d < dd) nz |= dl[d] != 0.f;
+  if (!nz) return;  // the zeroed workspace already holds this sum
+  const bool enters = lane == 0 && jp == j;
+  const bool leaves = j63 == j && jn == j;
+  // one writer per location: a vertex has one run, a wave has one entering and one leaving run
+  float* dst = (enters || leaves) ? part + ((e >> 6) * 2 + (enters ? 0 : 1)) * dd : delta + (long)j * dd;
+#pragma unroll
+  for (int d = 0; d < DM; ++d)
+    if (d < dd) dst[d] = dl[d];
+}
+
+// One thread per (vertex, coordinate): a vertex whose edge run [indptr[j], indptr[j + 1]) spans
+// several waves gets delta = the waves' partial sums added in ascending wave order (the run's
+// first wave filed its partial under side 1, every later one under side 0); with emb != null the
+// layout is advanced, emb += delta.
+__global__ __launch_bounds__(256) void umap_sync_fold_kernel(const long long* __restrict__ indptr, long n_vertices,
+                                                             int dim, float* __restrict__ delta,
+                                                             const float* __restrict__ part,
+                                                             float* __restrict__ emb) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_vertices * dim) return;
+  const long j = i / dim;
+  const int d = (int)(i - j * dim);
+  const long long e0 = indptr[j], e1 = indptr[j + 1];
+  float s = delta[i];
+  if (e1 > e0 && ((e1 - 1) >> 6) > (e0 >> 6)) {
+    const long w0 = e0 >> 6, w1 = (e1 - 1) >> 6;
+    s = part[(w0 * 2 + 1) * dim + d];
+    for (long w = w0 + 1; w <= w1; ++w) s += part[(w * 2) * dim + d];
+    delta[i] = s;
+  }
+  if (emb != nullptr) emb[i] += s;
+}
+
 }  // namespace
 
 namespace {
@@ -253,6 +428,51 @@ SRML_API int srml_umap_epoch(const int* head, const int* tail, long n_edges, con
     default: SRML_UMAP_LAUNCH(0); break;
   }
 #undef SRML_UMAP_LAUNCH
+  return srml_status();
+}
+
+// Workspace of srml_umap_epoch_sync in floats: delta [n_head_vertices][dim], then one
+// [2][dim] slot pair per 64-edge wave.
+SRML_API long srml_umap_epoch_sync_ws(long n_edges, long n_head_vertices, int dim) {
+  return n_head_vertices * (long)dim + 2 * ((n_edges + 63) / 64) * (long)dim;
+}
+
+// Synchronous epoch (see umap_epoch_sync_kernel): head / tail int32 head-sorted edges, indptr
+// int64 [n_head_vertices + 1] = the CSR row pointer of head. emb_head and emb_tail are only read
+// by the edge kernel; ws (srml_umap_epoch_sync_ws floats) starts with delta [n_head_vertices][dim],
+// the epoch's summed head moves. apply != 0 also advances the layout, emb_head += delta.
+// move_other without pull would write tails: -8.
+SRML_API int srml_umap_epoch_sync(const int* head, const int* tail, long n_edges, const long long* indptr,
+                                  const float* eps, float* next_sample, float* next_neg, const float* eps_neg,
+                                  float* emb_head, const float* emb_tail, long n_head_vertices, int n_tail_vertices,
+                                  int dim, float a, float b, float gamma, float alpha, float epoch, int move_other,
+                                  int pull, unsigned seed, const float* neg_tab, const int* neg_ids, int neg_lines,
+                                  float* ws, int apply, hipStream_t stream) {
+  if (move_other && !pull) return -8;
+  if (dim < 1 || dim > 32 || n_tail_vertices < 1 || n_head_vertices < 1 || !indptr || !ws) return -8;
+  if (n_edges <= 0) return 0;
+  if ((n_head_vertices * (long)dim + 255) / 256 > srml_max_blocks(256)) return -8;
+  float* delta = ws;
+  float* part = ws + n_head_vertices * (long)dim;
+  if (hipMemsetAsync(ws, 0, sizeof(float) * (size_t)srml_umap_epoch_sync_ws(n_edges, n_head_vertices, dim), stream) !=
+      hipSuccess)
+    return srml_status();
+  const dim3 grid((unsigned)((n_edges + 255) / 256));
+#define SRML_UMAP_LAUNCH(DD)                                                                                         \
+  hipLaunchKernelGGL(umap_epoch_sync_kernel<DD>, grid, dim3(256), 0, stream, head, tail, n_edges, eps, next_sample,  \
+                     next_neg, eps_neg, emb_head, emb_tail, n_tail_vertices, dim, a, b, gamma, alpha, epoch, pull,   \
+                     seed, neg_tab, neg_ids, neg_lines, delta, part)
+  switch (dim) {
+    case 2: SRML_UMAP_LAUNCH(2); break;
+    case 3: SRML_UMAP_LAUNCH(3); break;
+    case 4: SRML_UMAP_LAUNCH(4); break;
+    case 8: SRML_UMAP_LAUNCH(8); break;
+    case 16: SRML_UMAP_LAUNCH(16); break;
+    default: SRML_UMAP_LAUNCH(0); break;
+  }
+#undef SRML_UMAP_LAUNCH
+  hipLaunchKernelGGL(umap_sync_fold_kernel, dim3(ceil_div(n_head_vertices * (long)dim, 256)), dim3(256), 0, stream,
+                     indptr, n_head_vertices, dim, delta, part, apply ? emb_head : nullptr);
   return srml_status();
 }
 

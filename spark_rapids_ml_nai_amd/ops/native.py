@@ -30,6 +30,7 @@ _LONG_RESULT = ("srml_rf_bootstrap_ws", "srml_logreg_fold_ws", "srml_qn_mb_scrat
                 "srml_qn_fused_barrier_offset",
                 "srml_logreg_fold_parts", "srml_qn_args_size", "srml_logit_residual_ws", "srml_xtv_mfma_ws",
                 "srml_rf_partition_ws", "srml_dbscan_labels_ws", "srml_umap_categorical_ws",
+                "srml_umap_epoch_sync_ws",
                 "srml_label_sort_ws", "srml_radix_sort_ws", "srml_lloyd_moved_ws", "srml_sum_f32_ws", "srml_sum_sq_ws")
 SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_col_moments_f32": (_P, _L, _I, _L, _P, _P, _P),
@@ -154,6 +155,9 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_umap_epoch": (_P, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _I, _I, ctypes.c_uint, _P, _P,
                         _I, _P),
     "srml_umap_neg_table": (_P, _P, _L, _I, _P, _P),
+    "srml_umap_epoch_sync_ws": (_L, _L, _I),
+    "srml_umap_epoch_sync": (_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _F, _F, _I, _I,
+                             ctypes.c_uint, _P, _P, _I, _P, _I, _P),
     "srml_syevj_f64": (_P, _I, _P, _P, _I, _D, _P),
     "srml_potrf_f64": (_P, _I, _L, _P, _P),
     "srml_potrs_f64": (_P, _I, _L, _P, _P),

@@ -283,6 +283,8 @@ def _worker_env(spark: Any) -> Dict[str, str]:
     env = {"SRML_COMM": spark_comm_mode(spark)}
     if str(spark.conf.get("spark.rocm.ml.uvm.enabled", "false")).lower() == "true":
         env["SRML_UVM"] = "1"
+    if str(spark.conf.get("spark.rocm.ml.deterministic", "false")).lower() == "true":
+        env["SRML_DETERMINISTIC"] = "1"  # utils/determinism.py: the UMAP job's synchronous epochs among others
     return env
 
 
