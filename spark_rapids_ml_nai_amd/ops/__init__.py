@@ -2707,30 +2707,40 @@ def spd_factor_solve(L: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def _cd_gram_global(A: torch.Tensor, b: torch.Tensor, l1: torch.Tensor, l2: torch.Tensor, max_iter: int, tol: float,
+                    w: torch.Tensor, warm: bool) -> Tuple[torch.Tensor, int]:
+    """Global-memory block-cyclic sweeps (any n; ``cd_gram`` uses them past the LDS-resident
+    kernels): one launch sequence per sweep, the convergence word read once per sweep. ``w`` is the
+    start vector, updated in place; ``warm`` = it is not all zero, so g = A w is computed first."""
+    n = A.shape[0]
+    A = A.double().contiguous()
+    g = zeros(n, dtype=torch.float64, device=A.device)
+    dv = zeros(64, dtype=torch.float64, device=A.device)
+    stats = zeros(2, dtype=torch.float64, device=A.device)
+    bb, l1c, l2c = _c(b.double()), _c(l1.double()), _c(l2.double())
+    st = native.stream(A.device)
+    it = 0
+    for it in range(1, max(1, max_iter) + 1):
+        stats.zero_()
+        native.call("srml_cd_sweep_global_f64", A.data_ptr(), n, A.stride(0), bb.data_ptr(), l1c.data_ptr(),
+                    l2c.data_ptr(), w.data_ptr(), g.data_ptr(), dv.data_ptr(), stats.data_ptr(),
+                    int(it == 1 and warm), st)
+        md, mw = stats.tolist()
+        if md <= tol * max(mw, 1e-300):
+            break
+    return w, it
+
+
 def cd_gram(A: torch.Tensor, b: torch.Tensor, l1: torch.Tensor, l2: torch.Tensor, max_iter: int, tol: float,
             w0: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, int]:
-    """Cyclic coordinate descent: argmin 1/2 w'Aw - b'w + sum l1|w| + 1/2 sum l2 w^2 (fp64)."""
+    """Cyclic coordinate descent: argmin 1/2 w'Aw - b'w + sum l1|w| + 1/2 sum l2 w^2 (fp64).
+    At least one sweep runs on every path (``max_iter`` < 1 means 1)."""
     n = A.shape[0]
+    max_iter = max(1, int(max_iter))
     w = (zeros(n, dtype=torch.float64, device=A.device) if w0 is None else w0.double().clone()).contiguous()
     if A.is_cuda and 2 * n * 8 > 150 * 1024:
-        # wider than the LDS-resident kernels: global-memory block-cyclic sweeps, one launch
-        # sequence per sweep, the convergence word read once per sweep
-        A = A.double().contiguous()
-        g = zeros(n, dtype=torch.float64, device=A.device)
-        dv = zeros(64, dtype=torch.float64, device=A.device)
-        stats = zeros(2, dtype=torch.float64, device=A.device)
-        bb, l1c, l2c = _c(b.double()), _c(l1.double()), _c(l2.double())
-        st = native.stream(A.device)
-        it = 0
-        for it in range(1, max(1, max_iter) + 1):
-            stats.zero_()
-            native.call("srml_cd_sweep_global_f64", A.data_ptr(), n, A.stride(0), bb.data_ptr(), l1c.data_ptr(),
-                        l2c.data_ptr(), w.data_ptr(), g.data_ptr(), dv.data_ptr(), stats.data_ptr(),
-                        int(it == 1 and w0 is not None), st)
-            md, mw = stats.tolist()
-            if md <= tol * max(mw, 1e-300):
-                break
-        return w, it
+        # wider than the LDS-resident kernels
+        return _cd_gram_global(A, b, l1, l2, max_iter, tol, w, w0 is not None)
     if not A.is_cuda:
         Ah, bh, l1h, l2h = (t.double().cpu().numpy() for t in (A, b, l1, l2))
         wh = w.cpu().numpy()

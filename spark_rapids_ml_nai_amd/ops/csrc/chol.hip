@@ -10,6 +10,9 @@
 //    (Spark/cuML elastic-net objective on the standardised Gram matrix, "covariance updates"):
 //    one 1024-thread workgroup keeps w and A·w in LDS, each coordinate update streams one row
 //    of A (L2-resident) — the whole solve is one kernel launch instead of a host loop.
+//  * srml_potrf_f64_variant / srml_potrs_f64_variant / srml_cd_gram_f64_variant: the same entry
+//    points with the kernel choice (otherwise made from n or the environment) as an argument, so
+//    every kernel can be run at any size (tests/test_dense_solvers.py).
 // Reference: cuML LinearRegressionMG / RidgeMG / CDMG solves (regression.py:498-613).
 #include "common.h"
 
@@ -608,13 +611,14 @@ __global__ __launch_bounds__(1024) void cd_gram_pipe_kernel(const double* __rest
 }
 }  // namespace
 
-SRML_API int srml_potrf_f64(double* A, int n, long lda, int* info, hipStream_t stream) {
+// Cholesky with every kernel choice explicit (tests and tuning reach each kernel at any n):
+// nb = panel width (32 or 64), diag_reg = 1 the one-wave register diagonal block / 0 the LDS one,
+// syrk = 1 lower-triangle trailing update / 0 the full DGEMM. Anything else: -1.
+SRML_API int srml_potrf_f64_variant(double* A, int n, long lda, int* info, int nb_sel, int diag_reg, int syrk,
+                                    hipStream_t stream) {
+  if ((nb_sel != 32 && nb_sel != NB_MAX) || (diag_reg != 0 && diag_reg != 1) || (syrk != 0 && syrk != 1)) return -1;
   if (n <= 0) return 0;
-  // diagonal-block kernel: 1 = one wave, readlane broadcasts (64 us per 64 x 64 block); 0 = 256
-  // threads in LDS with two barriers per column. (One wave with the scaled pivot column shared
-  // through LDS broadcast reads measured 115 us: the chain is latency-bound, not readlane-bound.)
-  static const int diag_reg = getenv("SRML_POTRF_REG") ? atoi(getenv("SRML_POTRF_REG")) : 1;
-  static const int nbw = (getenv("SRML_POTRF_NB") && atoi(getenv("SRML_POTRF_NB")) == NB_MAX) ? NB_MAX : 32;
+  const int nbw = nb_sel;
   hipError_t err = hipSuccess;
   SRML_TRY(err, hipMemsetAsync(info, 0, sizeof(int), stream));
   for (int k0 = 0; k0 < n; k0 += nbw) {
@@ -637,8 +641,7 @@ SRML_API int srml_potrf_f64(double* A, int n, long lda, int* info, hipStream_t s
         hipLaunchKernelGGL(potrf_trsm_kernel<NB_MAX>, dim3((m2 + 255) / 256), dim3(256), 0, stream, A, lda, k0, k1, n);
       else
         hipLaunchKernelGGL(potrf_trsm_kernel<32>, dim3((m2 + 255) / 256), dim3(256), 0, stream, A, lda, k0, k1, n);
-      // trailing update A22 -= A21 A21^T on the lower-triangle tiles only (SRML_POTRF_SYRK=0: full)
-      static const int syrk = getenv("SRML_POTRF_SYRK") ? atoi(getenv("SRML_POTRF_SYRK")) : 1;
+      // trailing update A22 -= A21 A21^T on the lower-triangle tiles only (syrk = 0: full)
       const int rc = syrk ? srml_dgemm_syrk_lower(m2, nb, -1.0, A + (long)k1 * lda + k0, lda, 1.0,
                                                   A + (long)k1 * lda + k1, lda, stream)
                           : srml_dgemm(0, 1, m2, m2, nb, -1.0, A + (long)k1 * lda + k0, lda, A + (long)k1 * lda + k0,
@@ -650,19 +653,40 @@ SRML_API int srml_potrf_f64(double* A, int n, long lda, int* info, hipStream_t s
   return err != hipSuccess ? (int)err : st;
 }
 
-SRML_API int srml_potrs_f64(const double* L, int n, long lda, double* b, hipStream_t stream) {
+SRML_API int srml_potrf_f64(double* A, int n, long lda, int* info, hipStream_t stream) {
+  if (n <= 0) return 0;
+  // diagonal-block kernel: 1 = one wave, readlane broadcasts (64 us per 64 x 64 block); 0 = 256
+  // threads in LDS with two barriers per column. (One wave with the scaled pivot column shared
+  // through LDS broadcast reads measured 115 us: the chain is latency-bound, not readlane-bound.)
+  static const int diag_reg = getenv("SRML_POTRF_REG") ? atoi(getenv("SRML_POTRF_REG")) : 1;
+  static const int nbw = (getenv("SRML_POTRF_NB") && atoi(getenv("SRML_POTRF_NB")) == NB_MAX) ? NB_MAX : 32;
+  static const int syrk = getenv("SRML_POTRF_SYRK") ? atoi(getenv("SRML_POTRF_SYRK")) : 1;
+  return srml_potrf_f64_variant(A, n, lda, info, nbw, diag_reg ? 1 : 0, syrk ? 1 : 0, stream);
+}
+
+// variant 0 = potrs_blocked_kernel (n doubles of LDS + 41 KB static: n * 8 <= 110 KiB),
+// variant 1 = potrs_kernel, a row at a time (n * 8 <= 150 KiB); -9 past a kernel's limit.
+SRML_API int srml_potrs_f64_variant(const double* L, int n, long lda, double* b, int variant, hipStream_t stream) {
+  if (variant != 0 && variant != 1) return -1;
   if (n <= 0) return 0;
   const size_t lds = (size_t)n * sizeof(double);
-  if (lds > 150 * 1024) return -9;
-  if (lds <= 110 * 1024) {  // + 41 KB static (diagonal block, partial sums)
+  if (variant == 0) {
+    if (lds > 110 * 1024) return -9;
     (void)hipFuncSetAttribute((const void*)potrs_blocked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     hipLaunchKernelGGL(potrs_blocked_kernel, dim3(1), dim3(1024), lds, stream, L, n, lda, b, 0);
     return srml_status();
   }
+  if (lds > 150 * 1024) return -9;
   (void)hipFuncSetAttribute((const void*)potrs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(potrs_kernel, dim3(1), dim3(1024), lds, stream, L, n, lda, b);
   return srml_status();
+}
+
+SRML_API int srml_potrs_f64(const double* L, int n, long lda, double* b, hipStream_t stream) {
+  if (n <= 0) return 0;
+  const size_t lds = (size_t)n * sizeof(double);
+  return srml_potrs_f64_variant(L, n, lda, b, lds <= 110 * 1024 ? 0 : 1, stream);
 }
 
 // L^T x = z only (z = L^-1 b from the augmented factorisation of [A b; b^T c], whose last row
@@ -767,20 +791,25 @@ SRML_API int srml_cd_sweep_global_f64(const double* A, int n, long lda, const do
   return srml_status();
 }
 
-SRML_API int srml_cd_gram_f64(const double* A, int n, long lda, const double* b, const double* l1, const double* l2,
-                              double* w, int max_iter, double tol, int* iters, hipStream_t stream) {
+// variant 0 = cd_gram_pipe_kernel, 1 = cd_gram_block_kernel, 2 = cd_gram_kernel (row at a time);
+// each is refused with -9 when its LDS need exceeds 150 KiB.
+SRML_API int srml_cd_gram_f64_variant(const double* A, int n, long lda, const double* b, const double* l1,
+                                      const double* l2, double* w, int max_iter, double tol, int* iters, int variant,
+                                      hipStream_t stream) {
+  if (variant < 0 || variant > 2) return -1;
   if (n <= 0) return 0;
-  static const int pipe = getenv("SRML_CD_PIPE") ? atoi(getenv("SRML_CD_PIPE")) : 1;
-  const size_t lds_pipe = ((size_t)2 * n + CD_CB * (CD_CB + 1) + 18 * CD_CB) * sizeof(double);
-  if (pipe && lds_pipe <= 150 * 1024) {  // n <= ~6900
+  if (variant == 0) {
+    const size_t lds_pipe = ((size_t)2 * n + CD_CB * (CD_CB + 1) + 18 * CD_CB) * sizeof(double);
+    if (lds_pipe > 150 * 1024) return -9;  // n <= ~6900
     (void)hipFuncSetAttribute((const void*)cd_gram_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_pipe);
     hipLaunchKernelGGL(cd_gram_pipe_kernel, dim3(1), dim3(1024), lds_pipe, stream, A, n, lda, b, l1, l2, w, max_iter,
                        tol, iters, 0);
     return srml_status();
   }
-  const size_t lds_blk = ((size_t)2 * n + CD_CB * (CD_CB + 1) + CD_CB) * sizeof(double);
-  if (lds_blk <= 150 * 1024) {  // n <= ~7500
+  if (variant == 1) {
+    const size_t lds_blk = ((size_t)2 * n + CD_CB * (CD_CB + 1) + CD_CB) * sizeof(double);
+    if (lds_blk > 150 * 1024) return -9;  // n <= ~7500
     (void)hipFuncSetAttribute((const void*)cd_gram_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_blk);
     hipLaunchKernelGGL(cd_gram_block_kernel, dim3(1), dim3(1024), lds_blk, stream, A, n, lda, b, l1, l2, w, max_iter,
@@ -792,4 +821,14 @@ SRML_API int srml_cd_gram_f64(const double* A, int n, long lda, const double* b,
   (void)hipFuncSetAttribute((const void*)cd_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(cd_gram_kernel, dim3(1), dim3(1024), lds, stream, A, n, lda, b, l1, l2, w, max_iter, tol, iters);
   return srml_status();
+}
+
+SRML_API int srml_cd_gram_f64(const double* A, int n, long lda, const double* b, const double* l1, const double* l2,
+                              double* w, int max_iter, double tol, int* iters, hipStream_t stream) {
+  if (n <= 0) return 0;
+  static const int pipe = getenv("SRML_CD_PIPE") ? atoi(getenv("SRML_CD_PIPE")) : 1;
+  const size_t lds_pipe = ((size_t)2 * n + CD_CB * (CD_CB + 1) + 18 * CD_CB) * sizeof(double);
+  const size_t lds_blk = ((size_t)2 * n + CD_CB * (CD_CB + 1) + CD_CB) * sizeof(double);
+  const int variant = (pipe && lds_pipe <= 150 * 1024) ? 0 : (lds_blk <= 150 * 1024 ? 1 : 2);
+  return srml_cd_gram_f64_variant(A, n, lda, b, l1, l2, w, max_iter, tol, iters, variant, stream);
 }

@@ -42,6 +42,7 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_xw_f32": (_P, _L, _I, _L, _P, _I, _P, _P, _L, _P),
     "srml_dgemm": (_I, _I, _I, _I, _I, _D, _P, _L, _P, _L, _D, _P, _L, _P),
     "srml_dgemm_splitk": (_I, _I, _I, _I, _I, _D, _P, _L, _P, _L, _D, _P, _L, _I, _P, _P),
+    "srml_dgemm_syrk_lower": (_I, _I, _D, _P, _L, _D, _P, _L, _P),
     "srml_sign_flip_f64": (_P, _I, _I, _L, _P),
     "srml_xtv_f32": (_P, _L, _I, _L, _P, _I, _L, _P, _P),
     "srml_row_sqnorm_f32": (_P, _L, _I, _L, _P, _P),
@@ -163,6 +164,9 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_potrs_f64": (_P, _I, _L, _P, _P),
     "srml_potrs_backward_f64": (_P, _I, _L, _P, _P),
     "srml_cd_gram_f64": (_P, _I, _L, _P, _P, _P, _P, _I, _D, _P, _P),
+    "srml_potrf_f64_variant": (_P, _I, _L, _P, _I, _I, _I, _P),
+    "srml_potrs_f64_variant": (_P, _I, _L, _P, _I, _P),
+    "srml_cd_gram_f64_variant": (_P, _I, _L, _P, _P, _P, _P, _I, _D, _P, _I, _P),
     "srml_rf_quantize_u8": (_P, _L, _I, _L, _P, _I, _P, _P),
     "srml_rf_quantize_u8_ld": (_P, _L, _I, _L, _P, _I, _P, _L, _P),
     "srml_rf_pack_wy": (_P, _P, _P, _L, _P, _P),

@@ -51,7 +51,7 @@ def test_min_norm_solve_wide_device(gpu_device):
 @pytest.mark.gpu
 @pytest.mark.parametrize("fit_intercept", [True, False])
 @pytest.mark.parametrize("standardization", [True, False])
-@pytest.mark.parametrize("reg,l1", [(0.0, 0.0), (0.3, 0.0), (0.1, 0.5)])
+@pytest.mark.parametrize("reg,l1", [(0.0, 0.0), (0.3, 0.0), (0.1, 0.5), (0.1, 1.0)])
 def test_device_lsq_statistics_and_solve_match_cpu(gpu_device, fit_intercept, standardization, reg, l1):
     """The native second-order statistics (in-place all-reduce buffers, one-pass scatter shift, label
     sums) match the CPU pass (the device Gram's fp32 products: ~1e-6 relative), and on the SAME
