@@ -287,11 +287,13 @@ def nn_descent_refine(Xs: torch.Tensor, d2: torch.Tensor, pos: torch.Tensor, k: 
     N = Xs.shape[0]
     dev = Xs.device
     lo, hi = row_split(N, ctx)
+    a, b = min(int(a), k), min(int(b), k)  # the fan-out cannot exceed the graph's width
     for _ in range(max(0, int(iters))):
         tgt = pos.reshape(-1)
-        # reverse neighbours: edges grouped by target (stable: the source order is kept)
+        # reverse neighbours: edges grouped by target (stable: the source order is kept); padding
+        # edges (-1) are edges to nobody: out of [0, N) they trail after off[N] / lead before off[0]
         if tgt.is_cuda and N <= int(ops.native.lib().srml_label_sort_kmax()):
-            perm, off, _ = ops.label_sort(tgt.clamp_min(0).int(), N)
+            perm, off, _ = ops.label_sort(tgt.int(), N)
             perm = perm.long()
         else:
             srt, perm = torch.sort(tgt, stable=True)

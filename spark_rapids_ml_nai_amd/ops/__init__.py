@@ -609,13 +609,12 @@ def nearest_f16_labels(F: F16Planes, C: torch.Tensor) -> Optional[torch.Tensor]:
     """int32 arg-min labels of F's rows over the centres C on the fp16 planes (approximate: the
     filter's arg-min, lowest index on ties) in ONE pass per 256-row tile over all centres
     (``srml_nearest_f16_rowloop``: no per-(row, centre tile) slots), or None when the planes are not
-    128 halves wide (the caller takes ``nearest_centroid_f16(approx=True)``)."""
+    128 halves wide or a centre element left the plane's range (the caller takes
+    ``nearest_centroid_f16(approx=True)``, which re-searches exactly on overflow)."""
     if F.kp != 128 or os.environ.get("SRML_F16_ROWLOOP", "1") == "0":
         return None
     dev = F.X.device
-    # (the centre plane's overflow flag is not read: the callers' centres are Lloyd means of rows
-    # of X — convex combinations inside the range the plane's scale was chosen for)
-    _, cn, _, _, CP, crows = _f16_centre_planes(F, C, True)
+    _, cn, _, zero2, CP, crows = _f16_centre_planes(F, C, True)
     labels = torch.empty(F.m, dtype=torch.int32, device=dev)
     rc = native.lib().srml_nearest_f16_rowloop(F.P.data_ptr(), F.m, F.rows_pad, F.kp, CP.data_ptr(), C.shape[0],
                                                 crows, cn.data_ptr(), float(-2.0 / (F.scale * F.scale)),
@@ -624,6 +623,11 @@ def nearest_f16_labels(F: F16Planes, C: torch.Tensor) -> Optional[torch.Tensor]:
         return None
     if rc != 0:
         raise RuntimeError("srml_nearest_f16_rowloop failed (%d)" % rc)
+    # the centre plane's overflow flag (one host read per call, after the search is queued): the
+    # centres need not be means of F's own rows — knn_graph_ivf buckets one rank's row block
+    # against centres trained on a sample of all rows — and a clamped centre ranks too near
+    if int(zero2[0].item()):
+        return None
     return labels
 
 
