@@ -2,6 +2,8 @@
 
 * ``knn_graph_brute`` — exact: fused MFMA distance + LDS top-k (``ops.knn``); distributed, each
   rank queries its row block against the replicated X and the blocks are all-gathered.
+* ``knn_graph_metric`` — exact, for the metrics that are no Euclidean distance of transformed rows
+  (``ops.knn_metric``: the tiled VALU distance kernel + radix select); O(N^2), no approximate form.
 * ``knn_graph_ivf`` — approximate (the north-star 20M x 128 graph, BASELINE.json config 5):
   k-means lists, every 128-row query tile of a list matched against the ``nprobe`` lists
   nearest to its list's centroid by the MFMA tile kernel ``ops.knn_lists``, candidates
@@ -79,9 +81,28 @@ def knn_graph(Q: torch.Tensor, I: torch.Tensor, k: int) -> Tuple[torch.Tensor, t
     return torch.sqrt(d2.clamp_min(0)), idx
 
 
-def knn_graph_brute(X: torch.Tensor, k: int, ctx: Any = None) -> Tuple[torch.Tensor, torch.Tensor]:
+def is_euclidean(metric: str) -> bool:
+    """The metrics the Euclidean builders serve (cosine / correlation arrive as unit rows)."""
+    return str(metric).lower() in ("euclidean", "l2", "sqeuclidean")
+
+
+def knn_graph_metric(Q: torch.Tensor, I: torch.Tensor, k: int, metric: str,
+                     p: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact (distances [mq, k] fp32, indices [mq, k] int64) of Q's rows in I for the metrics of
+    ``ops.pairwise_dist`` (l1 / chebyshev / minkowski / canberra / hamming / jaccard / hellinger).
+    O(mq mi n) on the tiled distance kernel; ties go to the lower index."""
+    return ops.knn_metric(Q, I, k, metric, p)
+
+
+def knn_graph_brute(X: torch.Tensor, k: int, ctx: Any = None, metric: str = "euclidean",
+                    p: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact all-points graph; distributed, each rank queries its row block against the replicated
+    rows and the blocks are all-gathered. A non-Euclidean ``metric`` runs ``knn_graph_metric``."""
     lo, hi = row_split(X.shape[0], ctx)
-    dist, idx = knn_graph(X[lo:hi], X, k)
+    if is_euclidean(metric):
+        dist, idx = knn_graph(X[lo:hi], X, k)
+    else:
+        dist, idx = knn_graph_metric(X[lo:hi], X, k, metric, p)
     return gather_rows(dist, ctx), gather_rows(idx, ctx)
 
 
@@ -415,10 +436,22 @@ def knn_graph_ivf(X: torch.Tensor, k: int, nlist: Optional[int] = None, nprobe: 
 
 
 def build_knn_graph(X: torch.Tensor, k: int, build_algo: str = "auto", build_kwds: Optional[dict] = None,
-                    seed: int = 0, ctx: Any = None, list_order: bool = False, phases: Optional[dict] = None) -> Any:
+                    seed: int = 0, ctx: Any = None, list_order: bool = False, phases: Optional[dict] = None,
+                    metric: str = "euclidean", p: float = 2.0) -> Any:
     """(dist, idx); with ``list_order`` (dist, idx, order) where ``order`` is None unless the
-    builder left the graph in a locality order (see ``knn_graph_ivf``)."""
+    builder left the graph in a locality order (see ``knn_graph_ivf``).
+
+    ``metric`` / ``p``: a metric of ``ops.pairwise_dist`` is served by the exact chunked search
+    only: ``auto`` and ``brute_force_knn`` run it at ANY row count, which is O(N^2 n) work (the
+    100k-row switch to IVF lists applies to the Euclidean family alone); the IVF lists and the
+    NN-descent re-scoring are Euclidean throughout, so ``ivf`` / ``nn_descent`` raise."""
     algo = (build_algo or "auto").lower()
+    if not is_euclidean(metric):
+        if algo in ("ivf", "ivfflat", "ivf_flat", "nn_descent"):
+            raise ValueError("build_algo %r builds Euclidean graphs only; metric %r needs build_algo 'auto' or "
+                             "'brute_force_knn' (the exact search)" % (build_algo, metric))
+        if algo == "auto":
+            algo = "brute_force_knn"
     if algo == "auto":
         algo = "brute_force_knn" if X.shape[0] <= BRUTE_MAX_ROWS else "ivf"
     kw = dict(build_kwds or {})
@@ -426,7 +459,7 @@ def build_knn_graph(X: torch.Tensor, k: int, build_algo: str = "auto", build_kwd
         import time
 
         t0 = time.perf_counter()
-        d, i = knn_graph_brute(X, k, ctx)
+        d, i = knn_graph_brute(X, k, ctx, metric, p)
         lo, hi = row_split(X.shape[0], ctx)
         record_phase(phases, "knn_brute", hi - lo, t0, X.device)
         return (d, i, None) if list_order else (d, i)

@@ -2,6 +2,9 @@
 
 Semantics follow umap-learn / cuML UMAP (what the reference calls on one GPU, ``umap.py:924-958``):
 * kNN graph: exact, from the fused MFMA distance + top-k kernel (``ops.knn``), self included;
+  euclidean / l2 / sqeuclidean / cosine / correlation are Euclidean distances of transformed rows,
+  the other eleven metric names (l1 family, chebyshev / linf, minkowski, canberra, hamming, jaccard,
+  hellinger) use the tiled distance kernel + radix select (``ops.knn_metric``), exact graph only;
 * ``smooth_knn_dist`` (per-row bisection for sigma, rho = nearest non-zero distance with
   ``local_connectivity``) and the membership strengths exp(-(d - rho) / sigma) fused in one
   thread-per-row kernel (``ops.umap_smooth_knn``); torch reference on CPU;
@@ -92,6 +95,60 @@ def knn_graph(Q: torch.Tensor, I: torch.Tensor, k: int) -> Tuple[torch.Tensor, t
     d2, j = torch.sort(out, dim=1)
     idx = idx.gather(1, j)
     return torch.sqrt(d2.clamp_min(0)), idx
+
+
+def resolve_metric(metric: Any, metric_kwds: Optional[Dict[str, Any]] = None
+                   ) -> Tuple[str, Optional[str], Optional[str], float]:
+    """(kind, preprocessing, post-map, p) of a UMAP metric name, shared by fit and transform.
+
+    kind ``"euclidean"``: the Euclidean graph builders on rows preprocessed by ``_metric_rows``
+    (``None``, ``"unit"`` or ``"centred_unit"``), their distances mapped by ``_metric_dist``
+    (``None``, ``"square"`` or ``"half_square"``). Any other kind is a canonical name of
+    ``ops.pairwise_dist`` (exact graph on the tiled distance kernel, no pre- or post-map).
+    ``metric_kwds`` carries minkowski's ``p`` (default 2, finite, >= 1): p = 2 is euclidean, p = 1 l1."""
+    name = str(metric).lower()
+    kw = dict(metric_kwds or {})
+    if kw and name != "minkowski":
+        raise ValueError("metric_kwds %r given, but metric %r takes no argument (only minkowski takes p)"
+                         % (metric_kwds, metric))
+    if name in ("euclidean", "l2"):
+        return "euclidean", None, None, 2.0
+    if name == "sqeuclidean":
+        return "euclidean", None, "square", 2.0
+    if name == "cosine":
+        return "euclidean", "unit", "half_square", 2.0
+    if name == "correlation":
+        return "euclidean", "centred_unit", "half_square", 2.0
+    if name not in ops.PAIRDIST_ALIASES:
+        raise ValueError("Unsupported UMAP metric %r (euclidean, l2, sqeuclidean, cosine, correlation, %s)"
+                         % (metric, ", ".join(sorted(ops.PAIRDIST_ALIASES))))
+    if name == "minkowski":
+        if set(kw) - {"p"}:
+            raise ValueError("metric_kwds of minkowski: only 'p' is known, got %r" % sorted(kw))
+        p = float(kw.get("p", 2.0))
+        if not (p >= 1.0) or math.isinf(p):
+            raise ValueError("minkowski needs a finite p >= 1 in metric_kwds (got %r); use chebyshev for p = inf" % p)
+        if p == 2.0:
+            return "euclidean", None, None, 2.0
+        kind, p = ops.pairdist_metric(name, p)
+        return kind, None, None, p
+    return ops.pairdist_metric(name)[0], None, None, 2.0
+
+
+def _metric_rows(Xf: torch.Tensor, pre: Optional[str]) -> torch.Tensor:
+    if pre is None:
+        return Xf
+    if pre == "centred_unit":
+        Xf = Xf - Xf.mean(1, keepdim=True)
+    return Xf / Xf.norm(dim=1, keepdim=True).clamp_min(1e-30)
+
+
+def _metric_dist(dist: torch.Tensor, post: Optional[str]) -> torch.Tensor:
+    if post == "half_square":
+        return 0.5 * dist * dist  # 1 - cos for unit rows
+    if post == "square":
+        return dist * dist
+    return dist
 
 
 def smooth_knn_dist(dist: torch.Tensor, k: float, n_iter: int = 64, local_connectivity: float = 1.0,
@@ -545,13 +602,8 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
     a, b = params.get("a"), params.get("b")
     if a is None or b is None:
         a, b = find_ab_params(float(params.get("spread", 1.0)), float(params.get("min_dist", 0.1)))
-    Xf = X.float().contiguous()
-    if metric in ("cosine", "correlation"):
-        if metric == "correlation":
-            Xf = Xf - Xf.mean(1, keepdim=True)
-        Xf = Xf / Xf.norm(dim=1, keepdim=True).clamp_min(1e-30)
-    elif metric not in ("euclidean", "l2", "sqeuclidean"):
-        raise ValueError("Unsupported UMAP metric %r" % metric)
+    kind, pre_map, post_map, mink_p = resolve_metric(metric, params.get("metric_kwds"))
+    Xf = _metric_rows(X.float().contiguous(), pre_map)
     pre = params.get("precomputed_knn")
     order = None  # graph row i is original row order[i] (IVF list order), None: original order
     if pre is not None:
@@ -561,13 +613,10 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
         from .knn_graph import build_knn_graph
 
         g = build_knn_graph(Xf, k, params.get("build_algo", "auto"), params.get("build_kwds"), seed, ctx,
-                            list_order=LIST_ORDER, phases=phases)
+                            list_order=LIST_ORDER, phases=phases, metric=kind, p=mink_p)
         dist, idx, order = g if LIST_ORDER else (g[0], g[1], None)
         t_ph = time.perf_counter()  # the graph's phases are logged inside (synchronised)
-        if metric in ("cosine", "correlation"):
-            dist = 0.5 * dist * dist  # 1 - cos for unit rows
-        elif metric == "sqeuclidean":
-            dist = dist * dist
+        dist = _metric_dist(dist, post_map)
     lc = float(params.get("local_connectivity", 1.0))
     mix = float(params.get("set_op_mix_ratio", 1.0))
     if X.is_cuda:  # fused kernels: smooth_knn_dist + membership, then the kNN-structured union
@@ -626,17 +675,15 @@ def umap_transform(X: torch.Tensor, raw: torch.Tensor, embedding: torch.Tensor, 
     a, b = params.get("a"), params.get("b")
     if a is None or b is None:
         a, b = find_ab_params(float(params.get("spread", 1.0)), float(params.get("min_dist", 0.1)))
-    Xf, Rf = X.float().contiguous(), raw.float().contiguous()
-    if metric in ("cosine", "correlation"):
-        if metric == "correlation":
-            Xf, Rf = Xf - Xf.mean(1, keepdim=True), Rf - Rf.mean(1, keepdim=True)
-        Xf = Xf / Xf.norm(dim=1, keepdim=True).clamp_min(1e-30)
-        Rf = Rf / Rf.norm(dim=1, keepdim=True).clamp_min(1e-30)
-    dist, idx = knn_graph(Xf, Rf, k)
-    if metric in ("cosine", "correlation"):
-        dist = 0.5 * dist * dist
-    elif metric == "sqeuclidean":
-        dist = dist * dist
+    kind, pre_map, post_map, mink_p = resolve_metric(metric, params.get("metric_kwds"))
+    Xf, Rf = _metric_rows(X.float().contiguous(), pre_map), _metric_rows(raw.float().contiguous(), pre_map)
+    if kind == "euclidean":
+        dist, idx = knn_graph(Xf, Rf, k)
+    else:
+        from .knn_graph import knn_graph_metric
+
+        dist, idx = knn_graph_metric(Xf, Rf, k, kind, mink_p)
+    dist = _metric_dist(dist, post_map)
     adj_lc = max(0.0, float(params.get("local_connectivity", 1.0)) - 1.0)
     if X.is_cuda:
         _, _, w = ops.umap_smooth_knn(dist, idx, float(k), local_connectivity=adj_lc, self_rows=False)

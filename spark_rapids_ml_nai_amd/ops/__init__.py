@@ -1937,6 +1937,162 @@ def _knn_large_k(Q: torch.Tensor, I: torch.Tensor, k: int, inorm: Optional[torch
     return outv, outi
 
 
+# Metrics that are no Euclidean distance of transformed rows: name -> code of srml_pairdist_f32
+PAIRDIST_CODES = {"l1": 0, "linf": 1, "minkowski": 2, "canberra": 3, "hamming": 4, "jaccard": 5, "hellinger": 6}
+PAIRDIST_ALIASES = {"l1": "l1", "cityblock": "l1", "taxicab": "l1", "manhattan": "l1", "chebyshev": "linf",
+                    "linf": "linf", "minkowski": "minkowski", "canberra": "canberra", "hamming": "hamming",
+                    "jaccard": "jaccard", "hellinger": "hellinger"}
+_PAIRDIST_CPU_BYTES = 1 << 28  # broadcast (rows x items x features) budget of the torch form
+
+
+def pairdist_metric(metric: str, p: float = 2.0) -> Tuple[str, float]:
+    """(canonical name, p) of a ``pairwise_dist`` metric; aliases resolved, minkowski's p checked
+    (finite, >= 1; p = 1 is l1)."""
+    name = PAIRDIST_ALIASES.get(str(metric).lower())
+    if name is None:
+        raise ValueError("Unsupported pairwise metric %r (%s)" % (metric, ", ".join(sorted(PAIRDIST_ALIASES))))
+    if name != "minkowski":
+        return name, 2.0
+    p = float(p)
+    if not (p >= 1.0) or math.isinf(p):
+        raise ValueError("minkowski needs a finite p >= 1 (got %r); use chebyshev for p = inf" % p)
+    return ("l1", 2.0) if p == 1.0 else (name, p)
+
+
+def _pairdist_prepare(X: torch.Tensor, name: str) -> torch.Tensor:
+    """Rows as the distance kernel reads them: hellinger takes the square roots once."""
+    if not X.is_floating_point():
+        X = X.float()
+    if name == "hellinger":
+        if X.numel() and bool((X < 0).any()):
+            raise ValueError("hellinger distance needs non-negative input")
+        return torch.sqrt(X)
+    return X
+
+
+def _pairdist_expr(q: torch.Tensor, I: torch.Tensor, name: str, p: float) -> torch.Tensor:
+    """The metric table as a torch expression on prepared rows: [r, n] x [mi, n] -> [r, mi]."""
+    n = q.shape[1]
+    if name == "jaccard":
+        qa, ia = (q != 0).to(q.dtype), (I != 0).to(q.dtype)
+        inter = qa @ ia.T
+        uni = qa.sum(1).view(-1, 1) + ia.sum(1).view(1, -1) - inter
+        return torch.where(uni > 0, (uni - inter) / uni.clamp_min(1), torch.zeros_like(uni))
+    if name == "hellinger":
+        return torch.sqrt((1.0 - q @ I.T).clamp_min(0))
+    a, b = q.unsqueeze(1), I.unsqueeze(0)
+    if name == "hamming":
+        return (a != b).to(q.dtype).sum(-1) / n
+    t = (a - b).abs()
+    if name == "l1":
+        return t.sum(-1)
+    if name == "linf":
+        return t.amax(-1)
+    if name == "minkowski":
+        return t.pow(p).sum(-1).pow(1.0 / p)
+    s = a.abs() + b.abs()  # canberra: a 0 / 0 term counts 0
+    return torch.where(s > 0, t / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(t)).sum(-1)
+
+
+def _pairdist_torch(Q: torch.Tensor, I: torch.Tensor, name: str, p: float) -> torch.Tensor:
+    mq, n = Q.shape
+    mi = I.shape[0]
+    I = I.to(Q.dtype)
+    step = max(1, _PAIRDIST_CPU_BYTES // max(1, mi * n * Q.element_size()))
+    if mq <= step:
+        return _pairdist_expr(Q, I, name, p)
+    return torch.cat([_pairdist_expr(Q[s: s + step], I, name, p) for s in range(0, mq, step)])
+
+
+def _pairdist_native(Q: torch.Tensor, I: torch.Tensor, name: str) -> bool:
+    return Q.is_cuda and Q.dtype == torch.float32 and I.is_cuda and Q.shape[1] > 0
+
+
+def _pairdist_launch(Q: torch.Tensor, r: int, I: torch.Tensor, L: int, name: str, p: float, D: torch.Tensor) -> None:
+    """D[:r, :L] = d(Q[:r], I[:L]) on prepared fp32 device rows with unit column stride."""
+    native.call("srml_pairdist_f32", Q.data_ptr(), r, Q.shape[1], Q.stride(0), I.data_ptr(), L, I.stride(0),
+                PAIRDIST_CODES[name], float(p), D.data_ptr(), D.stride(0), native.stream(Q.device))
+
+
+def _unit_cols(t: torch.Tensor) -> torch.Tensor:
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def pairwise_dist(Q: torch.Tensor, I: torch.Tensor, metric: str, p: float = 2.0) -> torch.Tensor:
+    """D[q, i] = d(Q[q], I[i]) for the metrics no Euclidean kernel serves:
+
+    ========== ================================= ==========================================
+    l1         l1, cityblock, taxicab, manhattan sum |x - y|
+    linf       chebyshev, linf                   max |x - y|
+    minkowski  minkowski (``p`` >= 1)            (sum |x - y|^p)^(1/p)
+    canberra   canberra                          sum |x - y| / (|x| + |y|), 0/0 terms count 0
+    hamming    hamming                           #{x != y} / n
+    jaccard    jaccard                           1 - #{x != 0 and y != 0} / #{x != 0 or y != 0}
+                                                 (0 when both rows are all zero)
+    hellinger  hellinger                         sqrt(max(0, 1 - sum sqrt(x) sqrt(y))): cuML's
+                                                 un-normalised form, non-negative input
+    ========== ================================= ==========================================
+
+    fp32 device tensors: one launch of the tiled kernel ``srml_pairdist_f32`` (row strides kept);
+    CPU and fp64 tensors: the same table as a chunked torch expression."""
+    name, p = pairdist_metric(metric, p)
+    if Q.shape[1] != I.shape[1]:
+        raise ValueError("pairwise_dist: %d vs %d features" % (Q.shape[1], I.shape[1]))
+    Qp, Ip = _pairdist_prepare(Q, name), _pairdist_prepare(I, name)
+    if not _pairdist_native(Qp, Ip, name):
+        return _pairdist_torch(Qp, Ip, name, p)
+    Qp, Ip = _unit_cols(Qp), _unit_cols(Ip.float())
+    D = torch.empty((Q.shape[0], I.shape[0]), dtype=torch.float32, device=Q.device)
+    if D.numel():
+        _pairdist_launch(Qp, Q.shape[0], Ip, I.shape[0], name, p, D)
+    return D
+
+
+def knn_metric(Q: torch.Tensor, I: torch.Tensor, k: int, metric: str, p: float = 2.0,
+               id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact k nearest items of every query in a ``pairwise_dist`` metric: (distances fp32
+    [mq, k] ascending, item ids int64 [mq, k]; ties go to the lower id, k > mi pads +inf / -1).
+    O(mq mi n): per (query chunk, item chunk) the distances are materialised in one reused buffer
+    of at most ``_KNN_DIST_BYTES`` and selected by ``topk_rows``, which also merges the chunks.
+    The distances are sums of non-negative terms (no cancellation): no refine pass."""
+    name, p = pairdist_metric(metric, p)
+    mq, mi = Q.shape[0], I.shape[0]
+    Qp, Ip = _pairdist_prepare(Q, name), _pairdist_prepare(I, name)
+    if mq == 0 or mi == 0:
+        return (torch.full((mq, k), float("inf"), dtype=torch.float32, device=Q.device),
+                torch.full((mq, k), -1, dtype=torch.int64, device=Q.device))
+    if not _pairdist_native(Qp, Ip, name):
+        Ip = Ip.to(Qp.dtype)
+        step = max(1, _PAIRDIST_CPU_BYTES // max(1, mi * Q.shape[1] * Qp.element_size()))
+        parts = [topk_rows(_pairdist_expr(Qp[s: s + step], Ip, name, p), k, id_base=int(id_offset))
+                 for s in range(0, mq, step)]
+        return torch.cat([v for v, _ in parts]), torch.cat([i for _, i in parts])
+    Qp, Ip = _unit_cols(Qp), _unit_cols(Ip.float())
+    Lc = min(mi, 16 * _TOPK_SLICE, max(128, (_KNN_DIST_BYTES // (4 * 64)) // 128 * 128))
+    R = max(64, min(4096, (_KNN_DIST_BYTES // (Lc * 4)) // 64 * 64))
+    nchunks = (mi + Lc - 1) // Lc
+    outv = torch.empty((mq, k), dtype=torch.float32, device=Q.device)
+    outi = torch.empty((mq, k), dtype=torch.int64, device=Q.device)
+    D = torch.empty((min(R, mq), Lc), dtype=torch.float32, device=Q.device)
+    for q0 in range(0, mq, R):
+        r = min(R, mq - q0)
+        parts_v, parts_i = [], []
+        for c in range(nchunks):
+            i0 = c * Lc
+            L = min(Lc, mi - i0)
+            _pairdist_launch(Qp[q0:], r, Ip[i0:], L, name, p, D)
+            v, i = topk_rows(D[:r, :L], k, id_base=i0 + int(id_offset))
+            parts_v.append(v)
+            parts_i.append(i)
+        if nchunks > 1:
+            v, i = topk_rows(torch.cat(parts_v, 1), k, ids=torch.cat(parts_i, 1))
+        else:
+            v, i = parts_v[0], parts_i[0]
+        outv[q0: q0 + r] = v
+        outi[q0: q0 + r] = i
+    return outv, outi
+
+
 _IVF_CAND_BYTES = 1 << 30  # candidate matrix budget of the large-k IVF paths (distances + ids)
 
 

@@ -130,6 +130,7 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_nearest_centroid_f64": (_P, _L, _I, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P),
     "srml_row_sqnorm_f64": (_P, _L, _I, _L, _P, _P),
     "srml_knn_dist_f32": (_P, _L, _I, _L, _P, _L, _L, _P, _P, _L, _P),
+    "srml_pairdist_f32": (_P, _L, _I, _L, _P, _L, _L, _I, _F, _P, _L, _P),
     "srml_topk_rows_f32": (_P, _L, _L, _L, _I, _P, _L, ctypes.c_longlong, _I, _P, _P, _L, _L, _P),
     "srml_knn_f32": (_P, _L, _I, _L, _P, _L, _L, _P, _I, _I, _P, _P, ctypes.c_longlong, _P),
     "srml_ivf_search_f32": (_P, _L, _I, _L, _P, _I, _P, _P, _L, _P, _P, _I, _P, _P, _P),

@@ -6,7 +6,10 @@ sampled) dataset and the model keeps ``embedding_`` (N x n_components) and ``raw
 and the embedding columns (``umap.py:1149-1241``). Persistence writes the two matrices as
 ``.npy`` files next to the JSON metadata (``umap.py:1262-1327``).
 
-Supported: euclidean / l2 / sqeuclidean / cosine / correlation metrics, ``init`` spectral or
+Supported: the reference's sixteen metric names — euclidean / l2 / sqeuclidean / cosine /
+correlation on the Euclidean kNN kernels; l1 / cityblock / taxicab / manhattan, chebyshev / linf,
+minkowski (``metric_kwds={"p": ...}``), canberra, hamming, jaccard and hellinger on the tiled
+distance kernel (exact graph only, O(N^2)) — ``init`` spectral or
 random, supervised fits through ``labelCol`` (categorical target intersection), ``a``/``b``
 overrides, ``precomputed_knn`` (indices, distances), ``random_state``.
 """
@@ -34,8 +37,8 @@ from .core.params import (
 )
 from .parallel.context import WorkerContext
 
-_UMAP_KEYS = ("n_neighbors", "n_components", "metric", "n_epochs", "learning_rate", "init", "min_dist", "spread",
-              "set_op_mix_ratio", "local_connectivity", "repulsion_strength", "negative_sample_rate",
+_UMAP_KEYS = ("n_neighbors", "n_components", "metric", "metric_kwds", "n_epochs", "learning_rate", "init", "min_dist",
+              "spread", "set_op_mix_ratio", "local_connectivity", "repulsion_strength", "negative_sample_rate",
               "transform_queue_size", "a", "b", "precomputed_knn", "random_state", "build_algo", "build_kwds")
 
 
@@ -46,7 +49,8 @@ class UMAPClass(_BackendClass):
 
     def _get_backend_params_default(self) -> Dict[str, Any]:
         return {
-            "n_neighbors": 15, "n_components": 2, "metric": "euclidean", "n_epochs": None, "learning_rate": 1.0,
+            "n_neighbors": 15, "n_components": 2, "metric": "euclidean", "metric_kwds": None, "n_epochs": None,
+            "learning_rate": 1.0,
             "init": "spectral", "min_dist": 0.1, "spread": 1.0, "set_op_mix_ratio": 1.0, "local_connectivity": 1.0,
             "repulsion_strength": 1.0, "negative_sample_rate": 5, "transform_queue_size": 4.0, "a": None, "b": None,
             "precomputed_knn": None, "random_state": None, "build_algo": "auto", "build_kwds": None,
@@ -62,7 +66,12 @@ class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatures
     n_neighbors = _p("n_neighbors", "The size of local neighborhood used for manifold approximation.",
                      TypeConverters.toFloat)
     n_components = _p("n_components", "The dimension of the space to embed into.", TypeConverters.toInt)
-    metric = _p("metric", "Distance metric (euclidean, l2, sqeuclidean, cosine, correlation).", TypeConverters.toString)
+    metric = _p("metric", "Distance metric: euclidean, l2, sqeuclidean, cosine, correlation, l1, cityblock, taxicab, "
+                "manhattan, chebyshev, linf, minkowski, canberra, hamming, jaccard (non-zero patterns) or hellinger "
+                "(un-normalised, non-negative rows). The last eleven build the exact kNN graph only.",
+                TypeConverters.toString)
+    metric_kwds = _p("metric_kwds", "Arguments of the metric: {'p': ...} for minkowski (default 2, p >= 1); None "
+                     "for every other metric.", TypeConverters.identity)
     n_epochs = _p("n_epochs", "The number of training epochs (None: 500 for small, 200 for large datasets).",
                   TypeConverters.identity)
     learning_rate = _p("learning_rate", "The initial learning rate for the embedding optimization.",
@@ -92,7 +101,8 @@ class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatures
 
     def __init__(self) -> None:
         super().__init__()
-        self._setDefault(n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, learning_rate=1.0,
+        self._setDefault(n_neighbors=15, n_components=2, metric="euclidean", metric_kwds=None, n_epochs=None,
+                         learning_rate=1.0,
                          init="spectral", min_dist=0.1, spread=1.0, set_op_mix_ratio=1.0, local_connectivity=1.0,
                          repulsion_strength=1.0, negative_sample_rate=5, transform_queue_size=4.0, a=None, b=None,
                          precomputed_knn=None, random_state=None, sample_fraction=1.0, outputCol="embedding",
@@ -111,6 +121,12 @@ class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatures
         d = {k: self._backend_params.get(k) for k in _UMAP_KEYS}
         d["n_neighbors"] = int(d["n_neighbors"]) if d["n_neighbors"] is not None else 15
         return d
+
+    def _check_metric(self) -> None:
+        """Unknown metric, ``metric_kwds`` for a metric that takes none, minkowski p < 1: ValueError."""
+        from .models.umap import resolve_metric
+
+        resolve_metric(self._backend_params.get("metric", "euclidean"), self._backend_params.get("metric_kwds"))
 
     def _features(self, df: DataFrame) -> np.ndarray:
         fc = self.getFeaturesCol()
@@ -242,7 +258,8 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
 
     @keyword_only
     def __init__(self, *, n_neighbors: Optional[float] = 15, n_components: Optional[int] = 2,
-                 metric: str = "euclidean", n_epochs: Optional[int] = None, learning_rate: Optional[float] = 1.0,
+                 metric: str = "euclidean", metric_kwds: Optional[Dict[str, Any]] = None,
+                 n_epochs: Optional[int] = None, learning_rate: Optional[float] = 1.0,
                  init: Optional[str] = "spectral", min_dist: Optional[float] = 0.1, spread: Optional[float] = 1.0,
                  set_op_mix_ratio: Optional[float] = 1.0, local_connectivity: Optional[float] = 1.0,
                  repulsion_strength: Optional[float] = 1.0, negative_sample_rate: Optional[int] = 5,
@@ -253,6 +270,7 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
                  verbose: Union[int, bool] = False, **kwargs: Any) -> None:
         super().__init__()
         self._set_params(**self._input_kwargs)
+        self._check_metric()
 
     BROADCAST_LIMIT = 8 << 30
 
@@ -293,6 +311,7 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
     def _fit(self, dataset: Any) -> "UMAPModel":
         from .parallel.spark import is_spark_dataframe
 
+        self._check_metric()
         if is_spark_dataframe(dataset):
             emb, Xall = self._spark_fit(dataset)
             return self._make_model(emb, Xall)
