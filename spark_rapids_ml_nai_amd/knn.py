@@ -5,7 +5,8 @@ API parity with the reference ``knn.py``:
   column); ``NearestNeighborsModel.kneighbors(query_df)`` (558-624) returns
   ``(item_df_withid, query_df_withid, knn_df[query_<id>, indices, distances])``;
   ``exactNearestNeighborsJoin(query_df, distCol)`` (419-466, 753-782). Euclidean distances.
-* ``ApproximateNearestNeighbors`` (``knn.py:889-1118``): ``algorithm="ivfflat"`` (plus ``"brute"``),
+* ``ApproximateNearestNeighbors`` (``knn.py:889-1118``): ``algorithm="ivfflat"`` (plus ``"brute"``, and
+  ``"ivfpq"``, which the reference's docstring announces, 895-914, with cuML / cuVS parameter names),
   ``algoParams={"nlist", "nprobe"}``, metrics euclidean / l2 / sqeuclidean / inner_product
   (1307-1312); ``kneighbors`` and ``approxSimilarityJoin`` (1398-1427). One IVF index per item
   partition, as in the reference.
@@ -83,10 +84,15 @@ def _ivf_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarra
     import torch
 
     from .core.base import to_device
-    from .models.knn import build_ivf, exact_knn, ivf_knn
+    from .models.knn import build_ivf, build_ivfpq, check_pq_args, default_pq_m, exact_knn, ivf_knn, ivfpq_knn
 
-    items, item_ids, queries, query_ids, k, metric, algorithm, nlist, nprobe, seed, cache = payload
+    items, item_ids, queries, query_ids, k, metric, algorithm, nlist, nprobe, seed, cache = payload[:11]
+    pq = payload[11] if len(payload) > 11 else None  # (M, n_bits, refine_ratio): "ivfpq" only
     n = _agree_ncols(ctx, items, queries)
+    if algorithm == "ivfpq":
+        M, n_bits, refine_ratio = pq
+        M = int(M) if M is not None else default_pq_m(max(n, 1))
+        check_pq_args(n, M, int(n_bits), int(refine_ratio), k)  # same n on every rank: all raise alike
     Q = to_device(queries.reshape(-1, n), ctx.device, torch.float32)
     X = to_device(items.reshape(-1, n), ctx.device, torch.float32)
     ids = torch.as_tensor(item_ids, dtype=torch.int64).to(ctx.device)
@@ -94,6 +100,18 @@ def _ivf_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarra
         d, i = exact_knn(X, ids, Q, k, ctx, metric)
         return query_ids, i, d
     index = None
+    if algorithm == "ivfpq":
+        if X.shape[0] > 0:
+            nl = nlist if nlist else _default_nlist(X.shape[0])
+            key = ("ivfpq", int(nl), M, int(n_bits), int(seed))  # never the IVF-Flat slot, never other parameters
+            index = cache.get(key) if cache is not None else None
+            if index is None or index.items.device != X.device:
+                index = build_ivfpq(X, ids, nl, M, int(n_bits), seed)
+                if cache is not None:
+                    cache[key] = index
+        npb = nprobe if nprobe else _default_nprobe(index.centroids.shape[0] if index is not None else 1)
+        d, i = ivfpq_knn(index, Q, k, npb, int(refine_ratio), ctx, metric)
+        return query_ids, i, d
     if X.shape[0] > 0:
         index = cache.get("index") if cache is not None else None
         if index is None or index.items.device != X.device:
@@ -128,7 +146,9 @@ def _spark_knn_task(ctx: WorkerContext, table: Any, extra: Tuple[Any, ...]) -> A
     if ivf is None:
         qid, ind, dist = _exact_worker(ctx, (items, item_ids, queries, query_ids, k, metric))
     else:
-        qid, ind, dist = _ivf_worker(ctx, (items, item_ids, queries, query_ids, k, metric) + tuple(ivf) + (None,))
+        # ivf = (algorithm, nlist, nprobe, seed[, pq]): no index cache in a Spark task
+        qid, ind, dist = _ivf_worker(ctx, (items, item_ids, queries, query_ids, k, metric) + tuple(ivf[:4]) + (None,)
+                                     + tuple(ivf[4:]))
     yield _knn_batch(qname, np.asarray(qid, np.int64), np.asarray(ind), np.asarray(dist))
 
 
@@ -480,12 +500,37 @@ class _ANNParams(_NNParams):
         return self.getOrDefault(self.metric)
 
 
-_SUPPORTED_ALGOS = ("ivfflat", "brute")
+_SUPPORTED_ALGOS = ("ivfflat", "ivfpq", "brute")
 _SUPPORTED_METRICS = ("euclidean", "sqeuclidean", "l2", "inner_product")
+_PQ_MMAX = 128  # ops.PQ_MMAX (not imported here: the estimator classes load without torch)
+
+
+def _pq_params(ap: Dict[str, Any]) -> Tuple[Optional[int], int, int]:
+    """(M or None for the default, n_bits, refine_ratio) of ``algoParams`` for ``"ivfpq"``; the checks
+    that need no feature count. ``usePrecomputedTables`` (cuML) is accepted and ignored."""
+    def as_int(name: str, default: Optional[int]) -> Optional[int]:
+        v = ap.get(name, default)
+        if v is None:
+            return None
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("ivfpq: %s=%r must be an integer" % (name, v))
+        return int(v)
+
+    M, n_bits, refine_ratio = as_int("M", None), as_int("n_bits", 8), as_int("refine_ratio", 2)
+    if M is not None and not 1 <= M <= _PQ_MMAX:
+        raise ValueError("ivfpq: M=%d outside 1..%d" % (M, _PQ_MMAX))
+    if not 4 <= n_bits <= 8:
+        raise ValueError("ivfpq: n_bits=%d outside 4..8" % n_bits)
+    if refine_ratio < 1:
+        raise ValueError("ivfpq: refine_ratio=%d must be >= 1" % refine_ratio)
+    return M, n_bits, refine_ratio
 
 
 class ApproximateNearestNeighbors(ApproximateNearestNeighborsClass, _NoPersistence, _ANNParams):
     """IVF-Flat approximate kNN (``algoParams={"nlist": .., "nprobe": ..}``), one index per item partition.
+    ``algorithm="ivfpq"`` scans one-byte product-quantiser codes instead of the rows (``algoParams`` adds
+    ``M``, ``n_bits``, ``refine_ratio``; ``usePrecomputedTables`` is accepted and ignored) and re-scores
+    ``k * refine_ratio`` candidates exactly, so the returned distances are exact for the returned ids.
 
     >>> from spark_rapids_ml_nai_amd.knn import ApproximateNearestNeighbors
     >>> ann = ApproximateNearestNeighbors(k=2, algoParams={"nlist": 2, "nprobe": 2}, inputCol="features")
@@ -505,6 +550,8 @@ class ApproximateNearestNeighbors(ApproximateNearestNeighborsClass, _NoPersisten
             raise ValueError("algorithm %r is not supported; expected one of %s" % (self.getAlgorithm(), _SUPPORTED_ALGOS))
         if self.getMetric() not in _SUPPORTED_METRICS:
             raise ValueError("metric %r is not supported; expected one of %s" % (self.getMetric(), _SUPPORTED_METRICS))
+        if self.getAlgorithm() == "ivfpq":
+            _pq_params(dict(self.getAlgoParams() or {}))
 
     def fit(self, dataset: Any, params: Any = None) -> "ApproximateNearestNeighborsModel":
         est = self.copy(params) if isinstance(params, dict) else self
@@ -540,7 +587,11 @@ class ApproximateNearestNeighborsModel(ApproximateNearestNeighborsClass, _NNMode
     def _ivf_args(self) -> Optional[Tuple[Any, ...]]:
         ap = dict(self.getAlgoParams() or {})
         return (self.getAlgorithm(), ap.get("nlist", ap.get("n_lists")), ap.get("nprobe", ap.get("n_probes")),
-                int(ap.get("seed", 1)))
+                int(ap.get("seed", 1))) + self._pq_extra(ap)
+
+    def _pq_extra(self, ap: Dict[str, Any]) -> Tuple[Any, ...]:
+        """The trailing payload element of ``"ivfpq"``; the other algorithms' payloads stay as they were."""
+        return (_pq_params(ap),) if self.getAlgorithm() == "ivfpq" else ()
 
     def _payload_extra(self) -> Tuple[Any, ...]:
         ap = dict(self.getAlgoParams() or {})
@@ -549,7 +600,7 @@ class ApproximateNearestNeighborsModel(ApproximateNearestNeighborsClass, _NNMode
         # the built index is reusable across kneighbors calls only when the search runs in-process
         # (one worker, or one SPMD rank over its own item shard)
         cache = self._index_cache if (spmd_active() or max(1, self.num_workers) == 1) else None
-        return (self.getAlgorithm(), nlist, nprobe, int(ap.get("seed", 1)), cache)
+        return (self.getAlgorithm(), nlist, nprobe, int(ap.get("seed", 1)), cache) + self._pq_extra(ap)
 
     def kneighbors(self, query_df: Any, sort_knn_df_by_query_id: bool = True) -> Tuple[DataFrame, DataFrame, DataFrame]:
         """Approximate k nearest items of every query (see ``NearestNeighborsModel.kneighbors``)."""

@@ -1,4 +1,4 @@
-"""Distributed exact and IVF-Flat approximate k-nearest-neighbour search.
+"""Distributed exact and approximate (IVF-Flat, IVF-PQ) k-nearest-neighbour search.
 
 Reference: exact — cuML ``NearestNeighborsMG.kneighbors`` with UCX query fan-out and a partial
 top-k merge (``knn.py:638-749``; every item row id additionally travelled through the Spark
@@ -16,7 +16,12 @@ MI355X design (per rank = per item partition):
   chunk + radix-select path (k <= 1024) over the local items, candidates refined exactly;
 * IVF-Flat: coarse quantiser trained with the device KMeans kernels, items bucketed into
   contiguous inverted lists (device sort), probes chosen with the same top-k kernel against the
-  centroids, lists scanned by ``srml_ivf_search_f32``; queries ride the same ring.
+  centroids, lists scanned by ``srml_ivf_search_f32``; queries ride the same ring;
+* IVF-PQ (cuVS naming; the reference's docstring announces it, ``knn.py:895-914``): the same
+  quantiser and lists, every row stored as M one-byte codes of its residual to the list centre
+  (``srml_pq_encode_f32``, which is also the assignment step of the codebook training), the probed
+  lists scanned through an fp32 lookup table in LDS (``srml_ivfpq_search_f32`` /
+  ``srml_ivfpq_candidates_f32``) for ``k * refine_ratio`` candidates, which are re-scored exactly.
 """
 from __future__ import annotations
 
@@ -213,6 +218,114 @@ def ivf_knn(index: Optional[IVFIndex], queries: torch.Tensor, k: int, nprobe: in
         else:
             d, pos = ops.ivf_search(Q, probes.int(), index.list_off, index.items, index.inorm, pos_ids, k, qnorm=qn)
         d, pos = _refine_sorted(Q, index.items, pos, metric)
+        gi = torch.where(pos >= 0, index.ids[pos.clamp_min(0)], torch.full_like(pos, -1))
+        return _pad_k(d, gi, k)
+
+    d, gi = _ring_search(queries, k, ctx, local)
+    return _finish(d, metric).cpu().numpy(), gi.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------
+# IVF-PQ (cuVS / FAISS naming; beyond the reference version, whose docstring announces it)
+# ------------------------------------------------------------------------------------------
+@dataclass
+class IVFPQIndex:
+    centroids: torch.Tensor   # [nlist, n] coarse quantiser (build_ivf's)
+    cnorm: torch.Tensor
+    list_off: torch.Tensor    # [nlist + 1]
+    items: torch.Tensor       # [N, n] rows in list order: the exact re-score reads them
+    ids: torch.Tensor         # [N] item ids in list order
+    codebooks: torch.Tensor   # fp32 [M, ksub, dsub] over residuals x - c_list
+    codes: torch.Tensor       # uint8 [N, M], row-major, list order
+
+
+def default_pq_m(n: int) -> int:
+    """Largest divisor of n that is <= max(1, n // 4) (and <= ops.PQ_MMAX)."""
+    top = min(max(1, n // 4), ops.PQ_MMAX)
+    return max(m for m in range(1, top + 1) if n % m == 0)
+
+
+def check_pq_args(n: int, M: int, n_bits: int, refine_ratio: int, k: int) -> None:
+    """The checks of the IVF-PQ parameters that need the feature count (every rank raises alike)."""
+    if M < 1 or M > ops.PQ_MMAX:
+        raise ValueError("ivfpq: M=%d outside 1..%d" % (M, ops.PQ_MMAX))
+    if n % M != 0:
+        raise ValueError("ivfpq: M=%d does not divide the %d features" % (M, n))
+    if n_bits < 4 or n_bits > 8:
+        raise ValueError("ivfpq: n_bits=%d outside 4..8" % n_bits)
+    if refine_ratio < 1:
+        raise ValueError("ivfpq: refine_ratio=%d must be >= 1" % refine_ratio)
+    if k * refine_ratio > ops.TOPK_KMAX:
+        raise ValueError("ivfpq: k * refine_ratio = %d > %d" % (k * refine_ratio, ops.TOPK_KMAX))
+
+
+def train_pq(R: torch.Tensor, M: int, ksub: int, seed: int, iters: int = 10) -> torch.Tensor:
+    """Codebooks fp32 [M, ksub, dsub]: M independent Lloyd runs over the sub-vectors of the residual
+    rows R, seeded from ``seed``. The assignment of every run goes through ``ops.pq_encode`` in one
+    launch; the centre update is one ``ops.cluster_sums`` over the (run, codeword) pairs. A codeword
+    that ends without rows (fewer distinct training rows than ksub) copies codeword 0."""
+    T, n = R.shape
+    dsub = n // M
+    gen = torch.Generator().manual_seed(int(seed) + 0x5051)
+    Rv = R.float().contiguous().view(T, M, dsub)
+    cb = torch.empty((M, ksub, dsub), dtype=torch.float32, device=R.device)
+    take = min(T, ksub)
+    for m in range(M):  # its own rows for every run
+        sel = torch.randperm(T, generator=gen)[:take].to(R.device)
+        cb[m, :take] = Rv[:, m].index_select(0, sel)
+        cb[m, take:] = cb[m, :1]
+    base = (torch.arange(M, device=R.device, dtype=torch.int32) * ksub).view(1, M)
+    flat = Rv.view(T * M, dsub)
+    for _ in range(max(1, iters)):
+        lab = (ops.pq_encode(Rv.view(T, n), cb).int() + base).view(-1)
+        sums, counts = ops.cluster_sums(flat, lab, M * ksub)
+        new = (sums / counts.clamp_min(1).double().view(-1, 1)).float().view(M, ksub, dsub)
+        cb = torch.where(counts.view(M, ksub, 1) > 0, new, cb)
+    lab = (ops.pq_encode(Rv.view(T, n), cb).int() + base).view(-1)
+    used = ops.label_counts(lab, M * ksub).view(M, ksub, 1) > 0
+    return torch.where(used, cb, cb[:, :1].expand_as(cb)).contiguous()
+
+
+def build_ivfpq(X: torch.Tensor, ids: torch.Tensor, nlist: int, M: int, n_bits: int = 8, seed: int = 1,
+                iters: int = 20, pq_iters: int = 10, train_rows_per_code: int = 64) -> IVFPQIndex:
+    """``build_ivf``'s quantiser and list order, codebooks trained on the residuals of a row
+    subsample, and every row's residual encoded (row-major uint8 [N, M] in list order)."""
+    ivf = build_ivf(X, ids, nlist, seed, iters)
+    N, n = ivf.items.shape
+    ksub = 1 << int(n_bits)
+    nl = ivf.centroids.shape[0]
+    lab = torch.repeat_interleave(torch.arange(nl, device=X.device, dtype=torch.int32),
+                                  ivf.list_off[1:] - ivf.list_off[:-1], output_size=N)
+    ntrain = min(N, ksub * train_rows_per_code)
+    if ntrain < N:
+        gen = torch.Generator().manual_seed(int(seed) + 0x4956)
+        sel = torch.randperm(N, generator=gen)[:ntrain].to(X.device)
+        R = ivf.items.index_select(0, sel).float() - ivf.centroids.index_select(0, lab.index_select(0, sel).long())
+    else:
+        R = ivf.items.float() - ivf.centroids.index_select(0, lab.long())
+    cb = train_pq(R, M, ksub, seed, pq_iters)
+    codes = ops.pq_encode(ivf.items, cb, ivf.centroids, lab)
+    return IVFPQIndex(ivf.centroids, ivf.cnorm, ivf.list_off, ivf.items, ivf.ids, cb, codes)
+
+
+def ivfpq_knn(index: Optional[IVFPQIndex], queries: torch.Tensor, k: int, nprobe: int, refine_ratio: int,
+              ctx: WorkerContext, metric: str = "euclidean") -> Tuple[np.ndarray, np.ndarray]:
+    """Probe the coarse quantiser, take ``kc = k * refine_ratio`` candidates by PQ distance, re-score
+    them exactly against the list-ordered rows and keep k; queries ride the ring as for IVF-Flat."""
+    kc = int(k) * int(refine_ratio)
+    if kc > ops.TOPK_KMAX:
+        raise ValueError("ivfpq: k * refine_ratio = %d > %d" % (kc, ops.TOPK_KMAX))
+
+    def local(Q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if index is None:
+            return (torch.full((Q.shape[0], k), float("inf"), device=Q.device),
+                    torch.full((Q.shape[0], k), -1, dtype=torch.int64, device=Q.device))
+        npb = max(1, min(int(nprobe), index.centroids.shape[0], ops.KNN_KMAX))
+        _, probes = ops.knn(Q, index.centroids, npb, inorm=index.cnorm, qnorm=ops.row_sqnorm(Q))
+        _, pos = ops.ivfpq_search(Q, probes.int(), index.list_off, index.centroids, index.codebooks, index.codes, kc,
+                                  inner_product=metric == "inner_product")
+        d, pos = _refine_sorted(Q, index.items, pos, metric)
+        d, pos = d[:, :k], pos[:, :k]
         gi = torch.where(pos >= 0, index.ids[pos.clamp_min(0)], torch.full_like(pos, -1))
         return _pad_k(d, gi, k)
 

@@ -2174,6 +2174,163 @@ def ivf_search(Q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, it
     return (od + qnorm.float().view(-1, 1)).clamp_min(0), oi
 
 
+PQ_MMAX = 128     # sub-quantisers (csrc/ivfpq.hip PQ_MMAX)
+PQ_KSUBMAX = 256  # codewords per sub-quantiser: one byte per code
+
+
+def _pq_shapes(n: int, codebooks: torch.Tensor) -> Tuple[int, int, int]:
+    """(M, ksub, dsub) of fp32 codebooks [M, ksub, dsub] over n features; ValueError if they do not fit."""
+    if codebooks.dim() != 3:
+        raise ValueError("pq: codebooks must be [M, ksub, dsub], got %s" % (tuple(codebooks.shape),))
+    M, ksub, dsub = (int(v) for v in codebooks.shape)
+    if not 1 <= M <= PQ_MMAX:
+        raise ValueError("pq: M=%d outside 1..%d" % (M, PQ_MMAX))
+    if not 1 <= ksub <= PQ_KSUBMAX:
+        raise ValueError("pq: ksub=%d outside 1..%d" % (ksub, PQ_KSUBMAX))
+    if M * dsub != n or dsub < 1:
+        raise ValueError("pq: %d features do not split into M=%d sub-vectors of %d" % (n, M, dsub))
+    return M, ksub, dsub
+
+
+def _pq_refused(name: str, rc: int, n: int, M: int, ksub: int) -> None:
+    if rc == -9:
+        raise ValueError("%s: n=%d, M=%d, ksub=%d does not fit the kernel (lookup table of %d bytes in LDS)"
+                         % (name, n, M, ksub, M * ksub * 4))
+    if rc != 0:
+        raise RuntimeError("%s launch failed with HIP status %d" % (name, rc))
+
+
+def pq_encode(X: torch.Tensor, codebooks: torch.Tensor, centroids: Optional[torch.Tensor] = None,
+              labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Product-quantiser codes uint8 [N, M]: ``codes[r, m]`` is the arg-min over the ``ksub``
+    codewords of ``||(x_r - centroids[labels[r]])_m - codebooks[m, j]||^2`` (ties -> lower j;
+    without ``labels`` the rows are encoded as they are, e.g. residuals in training).
+    Device: ``srml_pq_encode_f32``; host: torch."""
+    N, n = X.shape
+    M, ksub, dsub = _pq_shapes(n, codebooks)
+    if (labels is None) != (centroids is None):
+        raise ValueError("pq_encode: centroids and labels go together")
+    if not X.is_cuda:
+        R = X.float() if labels is None else X.float() - centroids.float().index_select(0, labels.long())
+        cb = codebooks.float()
+        out = torch.empty((N, M), dtype=torch.uint8, device=X.device)
+        step = max(1, (1 << 24) // max(1, ksub * n))
+        for s in range(0, N, step):
+            r = R[s: s + step].view(-1, M, 1, dsub)
+            out[s: s + step] = ((r - cb.unsqueeze(0)) ** 2).sum(-1).argmin(-1).to(torch.uint8)
+        return out
+    Xc = X if X.dtype == torch.float32 and X.stride(1) == 1 else _c(X.float())
+    cbT = codebooks.float().transpose(1, 2).contiguous()  # [M, dsub, ksub]: lanes read over j
+    codes = torch.empty((N, M), dtype=torch.uint8, device=X.device)
+    lab = _c(labels.int()) if labels is not None else None
+    C = _c(centroids.float()) if centroids is not None else None
+    rc = native.call_status("srml_pq_encode_f32", Xc.data_ptr(), N, n, Xc.stride(0),
+                            lab.data_ptr() if lab is not None else None, int(C.shape[0]) if C is not None else 0,
+                            C.data_ptr() if C is not None else None, cbT.data_ptr(), M, ksub, codes.data_ptr(),
+                            native.stream(X.device))
+    _pq_refused("pq_encode", rc, n, M, ksub)
+    return codes
+
+
+def _ivfpq_large_k(Q: torch.Tensor, pr: torch.Tensor, lo: torch.Tensor, C: torch.Tensor, cbT: torch.Tensor,
+                   codes: torch.Tensor, M: int, ksub: int, k: int, ip: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """k > 64, as ``_ivf_large_k``: every (query, probe) writes its list's PQ keys and positions into
+    the query's candidate row (``srml_ivfpq_candidates_f32``); the radix-select kernel keeps k."""
+    dev = Q.device
+    nq, n = Q.shape
+    st = native.stream(dev)
+    nprobe = int(pr.shape[1])
+    od = torch.full((nq, k), float("inf"), dtype=torch.float32, device=dev)
+    oi = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+    if nprobe == 0:
+        return od, oi
+    cmax = zeros(1, dtype=torch.int64, device=dev)
+    native.call("srml_ivf_candidate_max", pr.data_ptr(), nprobe, None, nq, lo.data_ptr(), cmax.data_ptr(), st)
+    L = int(cmax.item())
+    if L == 0:
+        return od, oi
+    kk = min(k, L)
+    R = max(1, min(nq, _IVF_CAND_BYTES // (L * 12)))
+    D = torch.empty((R, L), dtype=torch.float32, device=dev)
+    DI = torch.empty((R, L), dtype=torch.int64, device=dev)
+    for q0 in range(0, nq, R):
+        r = min(R, nq - q0)
+        rc = native.call_status("srml_ivfpq_candidates_f32", Q.data_ptr(), q0, r, n, Q.stride(0), pr.data_ptr(), nprobe,
+                                lo.data_ptr(), int(lo.shape[0]) - 1, int(codes.shape[0]), C.data_ptr(), cbT.data_ptr(),
+                                codes.data_ptr(), M, ksub, ip, D.data_ptr(), DI.data_ptr(), L, st)
+        _pq_refused("ivfpq_search", rc, n, M, ksub)
+        v, i = topk_rows(D[:r], kk, ids=DI[:r])
+        od[q0: q0 + r, :kk] = v
+        oi[q0: q0 + r, :kk] = i
+    return od, oi
+
+
+def ivfpq_search(Q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
+                 codebooks: torch.Tensor, codes: torch.Tensor, k: int, inner_product: bool = False
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """IVF-PQ scan of each query's probed lists: (keys fp32 [nq, k] ascending, list-order positions
+    int64 [nq, k]; empty slots +inf / -1). ``codes`` is uint8 [N, M] in list order, ``codebooks``
+    fp32 [M, ksub, dsub] over residuals to the list centre. The key of an item is
+    ``||q - c_l - cb(item)||^2``, or ``-(q . c_l + q . cb(item))`` for ``inner_product``, summed
+    from a per-(query, list) fp32 lookup table. Device: ``srml_ivfpq_search_f32`` (k <= 64) or
+    ``srml_ivfpq_candidates_f32`` + ``topk_rows``; host: torch."""
+    nq, n = Q.shape
+    M, ksub, dsub = _pq_shapes(n, codebooks)
+    if k < 1 or k > TOPK_KMAX:
+        raise ValueError("ivfpq_search: k=%d outside 1..%d" % (k, TOPK_KMAX))
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M:
+        raise ValueError("ivfpq_search: codes must be uint8 [N, %d]" % M)
+    nlist = int(centroids.shape[0])
+    if list_off.shape[0] != nlist + 1:
+        raise ValueError("ivfpq_search: list_off has %d entries for %d lists" % (list_off.shape[0], nlist))
+    od = torch.full((nq, k), float("inf"), dtype=torch.float32, device=Q.device)
+    oi = torch.full((nq, k), -1, dtype=torch.int64, device=Q.device)
+    if nq == 0:
+        return od, oi
+    if not Q.is_cuda:
+        lo = list_off.cpu().numpy()
+        pr = probes.cpu().numpy()
+        cb = codebooks.float()
+        cd = codes.long()
+        marange = torch.arange(M).view(1, M)
+        for q in range(nq):
+            keys, rows = [], []
+            for l in pr[q]:
+                if l < 0 or l >= nlist or lo[l + 1] <= lo[l]:
+                    continue
+                r = torch.arange(int(lo[l]), int(lo[l + 1]))
+                if inner_product:
+                    lut = (cb * Q[q].float().view(M, 1, dsub)).sum(-1)  # [M, ksub]
+                    key = -((Q[q].float() * centroids[l].float()).sum() + lut[marange, cd[r]].sum(1))
+                else:
+                    lut = ((cb - (Q[q].float() - centroids[l].float()).view(M, 1, dsub)) ** 2).sum(-1)
+                    key = lut[marange, cd[r]].sum(1)
+                keys.append(key)
+                rows.append(r)
+            if not rows:
+                continue
+            r = torch.cat(rows)
+            v, j = torch.sort(torch.cat(keys), stable=True)
+            kk = min(k, v.shape[0])
+            od[q, :kk] = v[:kk]
+            oi[q, :kk] = r[j[:kk]]
+        return od, oi
+    Qc = Q if Q.dtype == torch.float32 and Q.stride(1) == 1 else _c(Q.float())
+    pr = _c(probes.int())
+    lo = _c(list_off.long())
+    C = _c(centroids.float())
+    cbT = codebooks.float().transpose(1, 2).contiguous()  # [M, dsub, ksub]: lanes read over j
+    cdc = _c(codes)
+    ip = int(bool(inner_product))
+    if k > KNN_KMAX:
+        return _ivfpq_large_k(Qc, pr, lo, C, cbT, cdc, M, ksub, k, ip)
+    rc = native.call_status("srml_ivfpq_search_f32", Qc.data_ptr(), nq, n, Qc.stride(0), pr.data_ptr(),
+                            int(pr.shape[1]), lo.data_ptr(), nlist, int(cdc.shape[0]), C.data_ptr(), cbT.data_ptr(),
+                            cdc.data_ptr(), M, ksub, ip, k, od.data_ptr(), oi.data_ptr(), native.stream(Q.device))
+    _pq_refused("ivfpq_search", rc, n, M, ksub)
+    return od, oi
+
+
 def knn_lists_f16_ok(X: torch.Tensor, k: int, centroids: Optional[torch.Tensor]) -> bool:
     """The centred fp16 candidate kernel applies (n <= 128, n % 4 == 0, k <= 32, fp32 rows)."""
     return (KNN_LISTS_F16 and centroids is not None and X.is_cuda and X.dtype == torch.float32

@@ -235,6 +235,9 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_cd_sweep_global_f64": (_P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _P),
     "srml_logit_residual_wide_f32": (_P, _L, _I, _L, _P, _P, _L, _P, _L, _P, _P, _P),
     "srml_logit_residual_wide_f64": (_P, _L, _I, _L, _P, _P, _L, _P, _L, _P, _P, _P),
+    "srml_pq_encode_f32": (_P, _L, _I, _L, _P, _I, _P, _P, _I, _I, _P, _P),
+    "srml_ivfpq_search_f32": (_P, _L, _I, _L, _P, _I, _P, _I, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P),
+    "srml_ivfpq_candidates_f32": (_P, _L, _L, _I, _L, _P, _I, _P, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _L, _P),
 }
 
 _lock = threading.Lock()
@@ -293,12 +296,17 @@ def stream(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def call_status(name: str, *args: Any) -> int:
+    """Launch ``name`` with its declared ctypes signature and return its status: for the entry
+    points whose negative statuses mean "refused" (the caller turns them into its own error)."""
+    if name not in SIGNATURES:
+        raise KeyError("native.call: %s has no entry in ops/native.py SIGNATURES" % name)
+    return int(getattr(lib(), name)(*args))
+
+
 def call(name: str, *args: Any) -> None:
     """Launch ``name`` with its declared ctypes signature. An entry point without one would get
     ctypes' default int conversion (64-bit pointers and sizes truncated), so it is refused."""
-    if name not in SIGNATURES:
-        raise KeyError("native.call: %s has no entry in ops/native.py SIGNATURES" % name)
-    fn = getattr(lib(), name)
-    rc = fn(*args)
+    rc = call_status(name, *args)
     if rc != 0:
         raise RuntimeError("%s launch failed with HIP status %d" % (name, rc))
