@@ -6,7 +6,8 @@ API parity with the reference ``knn.py``:
   ``(item_df_withid, query_df_withid, knn_df[query_<id>, indices, distances])``;
   ``exactNearestNeighborsJoin(query_df, distCol)`` (419-466, 753-782). Euclidean distances.
 * ``ApproximateNearestNeighbors`` (``knn.py:889-1118``): ``algorithm="ivfflat"`` (plus ``"brute"``, and
-  ``"ivfpq"``, which the reference's docstring announces, 895-914, with cuML / cuVS parameter names),
+  ``"ivfpq"``, which the reference's docstring announces, 895-914, with cuML / cuVS parameter names, and
+  ``"cagra"``, which its later releases ship, with the cuVS parameter names),
   ``algoParams={"nlist", "nprobe"}``, metrics euclidean / l2 / sqeuclidean / inner_product
   (1307-1312); ``kneighbors`` and ``approxSimilarityJoin`` (1398-1427). One IVF index per item
   partition, as in the reference.
@@ -84,11 +85,14 @@ def _ivf_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarra
     import torch
 
     from .core.base import to_device
-    from .models.knn import build_ivf, build_ivfpq, check_pq_args, default_pq_m, exact_knn, ivf_knn, ivfpq_knn
+    from .models.knn import (build_cagra, build_ivf, build_ivfpq, cagra_knn, check_cagra_args, check_pq_args,
+                             default_pq_m, exact_knn, ivf_knn, ivfpq_knn)
 
     items, item_ids, queries, query_ids, k, metric, algorithm, nlist, nprobe, seed, cache = payload[:11]
-    pq = payload[11] if len(payload) > 11 else None  # (M, n_bits, refine_ratio): "ivfpq" only
+    pq = payload[11] if len(payload) > 11 else None  # "ivfpq": (M, n_bits, refine_ratio); "cagra": _cagra_params
     n = _agree_ncols(ctx, items, queries)
+    if algorithm == "cagra":
+        check_cagra_args(pq, k, metric)  # the same on every rank: all raise alike
     if algorithm == "ivfpq":
         M, n_bits, refine_ratio = pq
         M = int(M) if M is not None else default_pq_m(max(n, 1))
@@ -100,6 +104,17 @@ def _ivf_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarra
         d, i = exact_knn(X, ids, Q, k, ctx, metric)
         return query_ids, i, d
     index = None
+    if algorithm == "cagra":
+        igd, gd, build_algo = pq[:3]
+        if X.shape[0] > 0:
+            key = ("cagra", int(igd), int(gd), build_algo, int(seed))  # build parameters only: a search-only
+            index = cache.get(key) if cache is not None else None      # parameter never forces a rebuild
+            if index is None or index.items.device != X.device:
+                index = build_cagra(X, ids, int(igd), int(gd), build_algo, seed)
+                if cache is not None:
+                    cache[key] = index
+        d, i = cagra_knn(index, Q, k, tuple(pq[3:]) + (int(seed),), ctx, metric)
+        return query_ids, i, d
     if algorithm == "ivfpq":
         if X.shape[0] > 0:
             nl = nlist if nlist else _default_nlist(X.shape[0])
@@ -146,7 +161,7 @@ def _spark_knn_task(ctx: WorkerContext, table: Any, extra: Tuple[Any, ...]) -> A
     if ivf is None:
         qid, ind, dist = _exact_worker(ctx, (items, item_ids, queries, query_ids, k, metric))
     else:
-        # ivf = (algorithm, nlist, nprobe, seed[, pq]): no index cache in a Spark task
+        # ivf = (algorithm, nlist, nprobe, seed[, pq or cagra parameters]): no index cache in a Spark task
         qid, ind, dist = _ivf_worker(ctx, (items, item_ids, queries, query_ids, k, metric) + tuple(ivf[:4]) + (None,)
                                      + tuple(ivf[4:]))
     yield _knn_batch(qname, np.asarray(qid, np.int64), np.asarray(ind), np.asarray(dist))
@@ -500,7 +515,7 @@ class _ANNParams(_NNParams):
         return self.getOrDefault(self.metric)
 
 
-_SUPPORTED_ALGOS = ("ivfflat", "ivfpq", "brute")
+_SUPPORTED_ALGOS = ("ivfflat", "ivfpq", "cagra", "brute")
 _SUPPORTED_METRICS = ("euclidean", "sqeuclidean", "l2", "inner_product")
 _PQ_MMAX = 128  # ops.PQ_MMAX (not imported here: the estimator classes load without torch)
 
@@ -526,11 +541,54 @@ def _pq_params(ap: Dict[str, Any]) -> Tuple[Optional[int], int, int]:
     return M, n_bits, refine_ratio
 
 
+_CAGRA_DMAX, _CAGRA_ITOPK_MAX, _CAGRA_CAND_MAX = 128, 512, 512  # ops.CAGRA_* (not imported here, as _PQ_MMAX)
+_CAGRA_BUILD_ALGOS = {"ivf_pq": "auto", "auto": "auto", "nn_descent": "nn_descent", "brute_force": "brute_force_knn"}
+_CAGRA_METRICS = ("euclidean", "l2", "sqeuclidean")
+
+
+def _cagra_params(ap: Dict[str, Any]) -> Tuple[int, int, str, int, int, int, int, int]:
+    """(intermediate_graph_degree, graph_degree, builder of ``build_knn_graph``, itopk_size rounded up to
+    a multiple of 32, search_width, max_iterations, min_iterations, num_random_samplings) of
+    ``algoParams`` for ``"cagra"`` (cuVS names); the checks that need no feature count."""
+    def as_int(name: str, default: int) -> int:
+        v = ap.get(name, default)
+        if v is None or isinstance(v, (bool, str)) or int(v) != v:
+            raise ValueError("cagra: %s=%r must be an integer" % (name, v))
+        return int(v)
+
+    igd, gd = as_int("intermediate_graph_degree", 128), as_int("graph_degree", 64)
+    if not 1 <= igd <= _CAGRA_DMAX:
+        raise ValueError("cagra: intermediate_graph_degree=%d outside 1..%d" % (igd, _CAGRA_DMAX))
+    if not 1 <= gd <= igd:
+        raise ValueError("cagra: graph_degree=%d outside 1..intermediate_graph_degree=%d" % (gd, igd))
+    algo = ap.get("build_algo", "ivf_pq")
+    if not isinstance(algo, str) or algo.lower() not in _CAGRA_BUILD_ALGOS:
+        raise ValueError("cagra: build_algo=%r not in %s" % (algo, sorted(_CAGRA_BUILD_ALGOS)))
+    if ap.get("compression") is not None:
+        raise ValueError("cagra: compression=%r is not supported (only None)" % (ap["compression"],))
+    itopk = as_int("itopk_size", 64)
+    if not 1 <= itopk <= _CAGRA_ITOPK_MAX:
+        raise ValueError("cagra: itopk_size=%d outside 1..%d" % (itopk, _CAGRA_ITOPK_MAX))
+    itopk = (itopk + 31) // 32 * 32
+    width = as_int("search_width", 1)
+    if width < 1 or width * gd > _CAGRA_CAND_MAX:
+        raise ValueError("cagra: search_width=%d x graph_degree=%d outside 1..%d" % (width, gd, _CAGRA_CAND_MAX))
+    max_it, min_it, nrs = as_int("max_iterations", 0), as_int("min_iterations", 0), as_int("num_random_samplings", 1)
+    if max_it < 0 or max_it > 65536 or min_it < 0 or nrs < 1:
+        raise ValueError("cagra: max_iterations=%d, min_iterations=%d, num_random_samplings=%d out of range"
+                         % (max_it, min_it, nrs))
+    as_int("seed", 1)
+    return igd, gd, _CAGRA_BUILD_ALGOS[algo.lower()], itopk, width, max_it, min_it, nrs
+
+
 class ApproximateNearestNeighbors(ApproximateNearestNeighborsClass, _NoPersistence, _ANNParams):
     """IVF-Flat approximate kNN (``algoParams={"nlist": .., "nprobe": ..}``), one index per item partition.
     ``algorithm="ivfpq"`` scans one-byte product-quantiser codes instead of the rows (``algoParams`` adds
     ``M``, ``n_bits``, ``refine_ratio``; ``usePrecomputedTables`` is accepted and ignored) and re-scores
     ``k * refine_ratio`` candidates exactly, so the returned distances are exact for the returned ids.
+    ``algorithm="cagra"`` builds a fixed-degree graph per item partition and walks it greedily on the device
+    (``algoParams``, cuVS names: ``intermediate_graph_degree``, ``graph_degree``, ``build_algo``, ``itopk_size``,
+    ``search_width``, ``max_iterations``, ``min_iterations``, ``num_random_samplings``; Euclidean metrics only).
 
     >>> from spark_rapids_ml_nai_amd.knn import ApproximateNearestNeighbors
     >>> ann = ApproximateNearestNeighbors(k=2, algoParams={"nlist": 2, "nprobe": 2}, inputCol="features")
@@ -552,6 +610,11 @@ class ApproximateNearestNeighbors(ApproximateNearestNeighborsClass, _NoPersisten
             raise ValueError("metric %r is not supported; expected one of %s" % (self.getMetric(), _SUPPORTED_METRICS))
         if self.getAlgorithm() == "ivfpq":
             _pq_params(dict(self.getAlgoParams() or {}))
+        if self.getAlgorithm() == "cagra":
+            if self.getMetric() not in _CAGRA_METRICS:  # the build graph is Euclidean
+                raise ValueError("metric %r is not supported by algorithm 'cagra'; expected one of %s"
+                                 % (self.getMetric(), _CAGRA_METRICS))
+            _cagra_params(dict(self.getAlgoParams() or {}))
 
     def fit(self, dataset: Any, params: Any = None) -> "ApproximateNearestNeighborsModel":
         est = self.copy(params) if isinstance(params, dict) else self
@@ -590,7 +653,10 @@ class ApproximateNearestNeighborsModel(ApproximateNearestNeighborsClass, _NNMode
                 int(ap.get("seed", 1))) + self._pq_extra(ap)
 
     def _pq_extra(self, ap: Dict[str, Any]) -> Tuple[Any, ...]:
-        """The trailing payload element of ``"ivfpq"``; the other algorithms' payloads stay as they were."""
+        """The trailing payload element of ``"ivfpq"`` / ``"cagra"``; the other algorithms' payloads stay as
+        they were."""
+        if self.getAlgorithm() == "cagra":
+            return (_cagra_params(ap),)
         return (_pq_params(ap),) if self.getAlgorithm() == "ivfpq" else ()
 
     def _payload_extra(self) -> Tuple[Any, ...]:

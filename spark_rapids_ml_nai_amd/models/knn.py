@@ -1,4 +1,4 @@
-"""Distributed exact and approximate (IVF-Flat, IVF-PQ) k-nearest-neighbour search.
+"""Distributed exact and approximate (IVF-Flat, IVF-PQ, CAGRA) k-nearest-neighbour search.
 
 Reference: exact — cuML ``NearestNeighborsMG.kneighbors`` with UCX query fan-out and a partial
 top-k merge (``knn.py:638-749``; every item row id additionally travelled through the Spark
@@ -21,7 +21,11 @@ MI355X design (per rank = per item partition):
   quantiser and lists, every row stored as M one-byte codes of its residual to the list centre
   (``srml_pq_encode_f32``, which is also the assignment step of the codebook training), the probed
   lists scanned through an fp32 lookup table in LDS (``srml_ivfpq_search_f32`` /
-  ``srml_ivfpq_candidates_f32``) for ``k * refine_ratio`` candidates, which are re-scored exactly.
+  ``srml_ivfpq_candidates_f32``) for ``k * refine_ratio`` candidates, which are re-scored exactly;
+* CAGRA (cuVS naming; the later releases of the reference ship it): per rank the all-points kNN
+  graph of ``models/knn_graph.py``, cut to a fixed degree by rank-based detour pruning and merged
+  with its reverse edges (``csrc/cagra.hip``), walked by ``srml_cagra_search_f32``: one workgroup
+  per query, the sorted candidate list, the visited hash and the query row in LDS.
 """
 from __future__ import annotations
 
@@ -326,6 +330,87 @@ def ivfpq_knn(index: Optional[IVFPQIndex], queries: torch.Tensor, k: int, nprobe
                                   inner_product=metric == "inner_product")
         d, pos = _refine_sorted(Q, index.items, pos, metric)
         d, pos = d[:, :k], pos[:, :k]
+        gi = torch.where(pos >= 0, index.ids[pos.clamp_min(0)], torch.full_like(pos, -1))
+        return _pad_k(d, gi, k)
+
+    d, gi = _ring_search(queries, k, ctx, local)
+    return _finish(d, metric).cpu().numpy(), gi.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------
+# CAGRA (cuVS naming; shipped by the later releases of the reference)
+# ------------------------------------------------------------------------------------------
+@dataclass
+class CagraIndex:
+    items: torch.Tensor   # [N, n] fp32, original order
+    ids: torch.Tensor     # [N] int64
+    graph: torch.Tensor   # [N, gd] int32, -1 padded at the tail
+
+
+def check_cagra_args(params: Tuple, k: int, metric: str) -> None:
+    """The checks of the CAGRA parameters (``knn._cagra_params``' tuple) that need k and the metric."""
+    if metric not in ("euclidean", "l2", "sqeuclidean"):
+        raise ValueError("cagra: metric %r is not supported (the build graph is Euclidean)" % (metric,))
+    itopk = int(params[3])
+    if k > itopk:
+        raise ValueError("cagra: k=%d exceeds itopk_size=%d" % (k, itopk))
+
+
+def build_cagra(X: torch.Tensor, ids: torch.Tensor, igd: int, gd: int, build_algo: str = "auto", seed: int = 1,
+                phases: Optional[dict] = None) -> CagraIndex:
+    """The kNN graph of ``build_knn_graph`` at ``igd + 1`` neighbours without each row's own index
+    (absent among duplicate rows: the last entry goes instead), detour-pruned to ``gd`` edges
+    (``ops.cagra_prune``) and merged with its reverse edges (``ops.cagra_merge``). Both degrees are
+    clamped to N - 1. ``phases`` (seconds): "knn_graph", "prune", "merge"."""
+    import time
+
+    from .knn_graph import build_knn_graph
+
+    N = int(X.shape[0])
+    Xf = X.float().contiguous()
+    igd = max(0, min(int(igd), N - 1))
+    gd = min(int(gd), igd)
+    if gd < 1:  # one row: no edge to give
+        return CagraIndex(Xf, ids, torch.full((N, 1), -1, dtype=torch.int32, device=X.device))
+
+    def lap(name: str, t0: float) -> float:
+        if phases is not None:
+            if X.is_cuda:
+                torch.cuda.synchronize(X.device)
+            phases[name] = phases.get(name, 0.0) + time.perf_counter() - t0
+        return time.perf_counter()
+
+    t0 = time.perf_counter()
+    _, idx = build_knn_graph(Xf, igd + 1, build_algo, seed=int(seed))
+    idx = idx.long()
+    own = idx == torch.arange(N, device=X.device).view(N, 1)
+    drop = torch.where(own.any(1), own.int().argmax(1), torch.full((N,), igd, device=X.device))
+    keep = torch.arange(igd + 1, device=X.device).view(1, -1) != drop.view(N, 1)
+    G = idx[keep].view(N, igd).to(torch.int32).contiguous()
+    t0 = lap("knn_graph", t0)
+    P = ops.cagra_prune(G, gd)
+    t0 = lap("prune", t0)
+    F = ops.cagra_merge(P, gd)
+    lap("merge", t0)
+    return CagraIndex(Xf, ids, F)
+
+
+def cagra_knn(index: Optional[CagraIndex], queries: torch.Tensor, k: int, params: Tuple, ctx: WorkerContext,
+              metric: str = "euclidean") -> Tuple[np.ndarray, np.ndarray]:
+    """Beam search of this rank's graph (``ops.cagra_search``) for the k best of the list, re-scored
+    exactly; queries ride the ring as for IVF-Flat. ``params`` = (itopk_size, search_width,
+    max_iterations, min_iterations, num_random_samplings, seed)."""
+    itopk, width, max_iter, min_iter, nrs, seed = (int(v) for v in params)
+    if k > itopk:
+        raise ValueError("cagra: k=%d exceeds itopk_size=%d" % (k, itopk))
+    S = min(itopk * nrs, ops.CAGRA_SEED_MAX)
+
+    def local(Q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if index is None:
+            return (torch.full((Q.shape[0], k), float("inf"), device=Q.device),
+                    torch.full((Q.shape[0], k), -1, dtype=torch.int64, device=Q.device))
+        _, pos = ops.cagra_search(Q, index.items, index.graph, k, itopk, width, max_iter, min_iter, S, seed)
+        d, pos = _refine_sorted(Q, index.items, pos, metric)
         gi = torch.where(pos >= 0, index.ids[pos.clamp_min(0)], torch.full_like(pos, -1))
         return _pad_k(d, gi, k)
 

@@ -2331,6 +2331,295 @@ def ivfpq_search(Q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, 
     return od, oi
 
 
+CAGRA_DMAX = 128        # intermediate and final graph degree (csrc/cagra.hip CG_DMAX)
+CAGRA_ITOPK_MAX = 512
+CAGRA_CAND_MAX = 512    # search_width * graph_degree
+CAGRA_SEED_MAX = 1024
+CAGRA_LDS_TOTAL = 160 * 1024
+_CAGRA_EMPTY = (1 << 63) - 1  # the empty key of the host path (int64; the device's is all ones)
+
+
+def _pow2(v: int) -> int:
+    p = 1
+    while p < v:
+        p <<= 1
+    return p
+
+
+def cagra_lds_bytes(n: int, itopk: int, width: int, gd: int, S: int, max_iter: int) -> int:
+    """LDS bytes of one ``srml_cagra_search_f32`` workgroup; mirrors ``cg_layout`` of csrc/cagra.hip
+    (``srml_cagra_lds_bytes``), which decides the launch: query row | list + candidate keys |
+    candidate ids | parents | visited table of >= 2 (S + max_iter * width * gd) slots | 64 static."""
+    c_init, c_iter = _pow2(S), _pow2(width * gd)
+    pmax = max(_pow2(itopk + c_init), _pow2(itopk + c_iter))
+    slots = max(2, _pow2(2 * (S + max_iter * width * gd)))
+    return ((n + 3) // 4) * 16 + pmax * 8 + max(c_init, c_iter) * 4 + ((width + 3) // 4) * 16 + slots * 4 + 64
+
+
+def cagra_auto_iters(n: int, itopk: int, width: int, gd: int, S: int) -> int:
+    """``max_iterations = 0``: itopk / width + 16, lowered to what the kernel's LDS holds (>= 1)."""
+    it = itopk // width + 16
+    while it > 1 and cagra_lds_bytes(n, itopk, width, gd, S, it) > CAGRA_LDS_TOTAL:
+        it -= 1
+    return it
+
+
+def _cagra_check(n: int, gd: int, k: int, itopk: int, width: int, max_iter: int, min_iter: int, S: int) -> int:
+    """The limits of ``cagra_search`` (both paths raise alike, nothing is launched); returns the
+    resolved ``max_iter``."""
+    if itopk < 32 or itopk > CAGRA_ITOPK_MAX or itopk % 32:
+        raise ValueError("cagra_search: itopk=%d must be a multiple of 32 in 32..%d" % (itopk, CAGRA_ITOPK_MAX))
+    if gd < 1 or gd > CAGRA_DMAX:
+        raise ValueError("cagra_search: graph degree %d outside 1..%d" % (gd, CAGRA_DMAX))
+    if width < 1 or width * gd > CAGRA_CAND_MAX:
+        raise ValueError("cagra_search: width * graph degree = %d * %d outside 1..%d" % (width, gd, CAGRA_CAND_MAX))
+    if k < 1 or k > itopk:
+        raise ValueError("cagra_search: k=%d outside 1..itopk=%d" % (k, itopk))
+    if S < 1 or S > CAGRA_SEED_MAX:
+        raise ValueError("cagra_search: %d seeds outside 1..%d" % (S, CAGRA_SEED_MAX))
+    if max_iter < 0 or max_iter > 65536 or min_iter < 0:
+        raise ValueError("cagra_search: max_iter=%d / min_iter=%d out of range" % (max_iter, min_iter))
+    if max_iter == 0:
+        max_iter = cagra_auto_iters(n, itopk, width, gd, S)
+    need = cagra_lds_bytes(n, itopk, width, gd, S, max_iter)
+    if need > CAGRA_LDS_TOTAL:
+        raise ValueError("cagra_search: n=%d, itopk=%d, width=%d, graph degree=%d, seeds=%d, max_iter=%d need %d "
+                         "bytes of LDS (visited table included), past the %d of a CU"
+                         % (n, itopk, width, gd, S, max_iter, need, CAGRA_LDS_TOTAL))
+    return max_iter
+
+
+def _mix32(h: torch.Tensor) -> torch.Tensor:
+    """murmur3's 32-bit finaliser on int64 tensors holding values < 2^32."""
+    m = 0xFFFFFFFF
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & m
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & m
+    return h ^ (h >> 16)
+
+
+def cagra_seeds(Q: torch.Tensor, N: int, S: int, seed: int = 1) -> torch.Tensor:
+    """Start nodes int32 [nq, S] of the graph search: entry (q, s) is
+    ``mix(rowhash(q) ^ mix(seed * 0x9E3779B9 + s * 0x85EBCA6B + 1)) mod N`` in 32-bit arithmetic, with
+    ``rowhash = sum_d mix(bits(Q[q, d]) ^ (d + 1) * 0x9E3779B9)`` over the fp32 bit patterns and
+    ``mix`` murmur3's finaliser: a function of the query row alone, not of its place in the batch.
+    Device: ``srml_cagra_seeds_i32``; host: the same integers in torch."""
+    nq, n = Q.shape
+    if N < 1 or N > 0x7FFFFFFF or S < 0:
+        raise ValueError("cagra_seeds: N=%d, S=%d out of range" % (N, S))
+    out = torch.empty((nq, S), dtype=torch.int32, device=Q.device)
+    if nq == 0 or S == 0:
+        return out
+    if not Q.is_cuda:
+        m = 0xFFFFFFFF
+        bits = Q.float().contiguous().view(torch.int32).long() & m
+        col = (torch.arange(1, n + 1, dtype=torch.int64) * 0x9E3779B9) & m
+        rh = _mix32(bits ^ col.view(1, n)).sum(1) & m
+        slot = ((int(seed) & m) * 0x9E3779B9 + torch.arange(S, dtype=torch.int64) * 0x85EBCA6B + 1) & m
+        return (_mix32(rh.view(nq, 1) ^ _mix32(slot).view(1, S)) % int(N)).to(torch.int32)
+    Qc = Q if Q.dtype == torch.float32 and Q.stride(1) == 1 else _c(Q.float())
+    rc = native.call_status("srml_cagra_seeds_i32", Qc.data_ptr(), nq, n, Qc.stride(0), int(N), int(S),
+                            int(seed) & 0xFFFFFFFF, out.data_ptr(), native.stream(Q.device))
+    if rc != 0:
+        raise RuntimeError("srml_cagra_seeds_i32 failed with status %d" % rc)
+    return out
+
+
+def _cagra_graph(G: torch.Tensor, gd: int, name: str) -> Tuple[int, int]:
+    if G.dim() != 2 or G.dtype != torch.int32:
+        raise ValueError("%s: the graph must be int32 [N, d], got %s %s" % (name, G.dtype, tuple(G.shape)))
+    N, d = int(G.shape[0]), int(G.shape[1])
+    if not 1 <= d <= CAGRA_DMAX or not 1 <= gd <= CAGRA_DMAX:
+        raise ValueError("%s: degrees d=%d, gd=%d outside 1..%d" % (name, d, gd, CAGRA_DMAX))
+    if N * max(d, gd) > 0x7FFFFFFF:
+        raise ValueError("%s: %d x %d edges do not fit 32-bit edge numbers" % (name, N, max(d, gd)))
+    return N, d
+
+
+def cagra_prune(G: torch.Tensor, gd: int) -> torch.Tensor:
+    """Rank-based detour pruning of a kNN graph ``G`` (int32 [N, d], rows in ascending distance,
+    distinct, without the row's own index, -1 only at the tail, d <= 128) to int32 [N, gd]:
+    ``detour(a, i)`` counts the ``j < i`` whose node ``c = G[a, j]`` has ``G[c, l] == G[a, i]`` for
+    some ``l < i``; row a keeps the gd ranks with the smallest (detour, rank), in that order, padded
+    with -1. Device: ``srml_cagra_prune_i32`` (block per node); host: torch."""
+    N, d = _cagra_graph(G, gd, "cagra_prune")
+    if gd > d:
+        raise ValueError("cagra_prune: gd=%d exceeds the %d columns of the graph" % (gd, d))
+    P = torch.empty((N, gd), dtype=torch.int32, device=G.device)
+    if N == 0:
+        return P
+    Gc = _c(G)
+    if Gc.is_cuda:
+        rc = native.call_status("srml_cagra_prune_i32", Gc.data_ptr(), N, d, gd, P.data_ptr(), native.stream(G.device))
+        if rc != 0:
+            raise RuntimeError("srml_cagra_prune_i32 failed with status %d" % rc)
+        return P
+    big = 0x7FFFFFFF
+    GL = Gc.long()
+    ar = torch.arange(d, dtype=torch.int64)
+    step = max(1, (1 << 22) // (d * d))
+    for s in range(0, N, step):
+        A = GL[s: s + step]
+        A = torch.where((A >= 0) & (A < N), A, torch.full_like(A, -1))
+        m = A.shape[0]
+        sval, srank = torch.sort(torch.where(A >= 0, A, torch.full_like(A, big)), dim=1, stable=True)
+        NB = GL[A.clamp_min(0)]                                          # [m, j, l]
+        NB = torch.where((A >= 0).view(m, d, 1) & (NB >= 0), NB, torch.full_like(NB, -1)).view(m, d * d)
+        pos = torch.searchsorted(sval, NB.contiguous()).clamp_max(d - 1)
+        hit = (sval.gather(1, pos) == NB) & (NB >= 0)
+        i = srank.gather(1, pos)
+        j = ar.repeat_interleave(d).view(1, -1)
+        l = ar.repeat(d).view(1, -1)
+        hit &= (i > j) & (i > l)
+        cnt = torch.zeros((m, d), dtype=torch.int64).scatter_add_(1, i, hit.long())
+        key = torch.where(A >= 0, cnt, torch.full_like(cnt, CAGRA_DMAX)) * CAGRA_DMAX + ar.view(1, d)
+        order = torch.argsort(key, dim=1)[:, :gd]
+        P[s: s + step] = A.gather(1, order).to(torch.int32)
+    return P
+
+
+def cagra_merge(P: torch.Tensor, gd: int) -> torch.Tensor:
+    """Reverse-edge merge of the pruned graph ``P`` (int32 [N, gd], -1 padded): ``rev[v]`` = the
+    sources u of the edges u -> v, ordered by (slot of v in P[u], u), first gd kept; with
+    ``h = gd // 2`` row v of the result is the first gd of ``P[v, :h]``, then the u of ``rev[v]``
+    not in ``P[v, :h]``, then the w of ``P[v, h:]`` not in ``rev[v]`` (-1 skipped, -1 padded).
+    The edges are grouped by ``radix_sort_pairs`` (stable, by target, over the slot-major edge
+    list), so no row depends on atomic arrival order: two calls give identical bytes. Device:
+    ``srml_cagra_merge_i32`` (wave per node) writes the rows; host: torch."""
+    N, _ = _cagra_graph(P, gd, "cagra_merge")
+    if P.shape[1] != gd:
+        raise ValueError("cagra_merge: P has %d columns, gd=%d" % (P.shape[1], gd))
+    F = torch.empty((N, gd), dtype=torch.int32, device=P.device)
+    if N == 0:
+        return F
+    Pc = _c(P)
+    h = gd // 2
+    tgt = Pc.t().contiguous().view(-1).long()                            # edge e = p * N + u -> its target
+    ok = (tgt >= 0) & (tgt < N)
+    keys = torch.where(ok, tgt, torch.full_like(tgt, N)).contiguous()    # edges without a target trail
+    src = torch.arange(N * gd, dtype=torch.int32, device=P.device)
+    radix_sort_pairs(keys, src, key_bits=max(1, int(N).bit_length()))
+    off = torch.searchsorted(keys, torch.arange(N + 1, dtype=torch.int64, device=P.device)).long().contiguous()
+    if Pc.is_cuda:
+        rc = native.call_status("srml_cagra_merge_i32", Pc.data_ptr(), N, gd, off.data_ptr(), src.data_ptr(), N * gd,
+                                F.data_ptr(), native.stream(P.device))
+        if rc != 0:
+            raise RuntimeError("srml_cagra_merge_i32 failed with status %d" % rc)
+        return F
+    e = torch.arange(N * gd, dtype=torch.int64)
+    slot = e - off[keys.clamp_max(N - 1)]
+    keep = (keys < N) & (slot < gd)
+    R = torch.full((N, gd), -1, dtype=torch.int64)
+    R[keys[keep], slot[keep]] = src[keep].long() % N
+    Pl = torch.where((Pc >= 0) & (Pc < N), Pc, torch.full_like(Pc, -1)).long()
+    step = max(1, (1 << 22) // (gd * gd))
+    for s in range(0, N, step):
+        p, r = Pl[s: s + step], R[s: s + step]
+        head, tail = p[:, :h], p[:, h:]
+        r_new = torch.where((r.unsqueeze(2) == head.unsqueeze(1)).any(2), torch.full_like(r, -1), r)
+        t_new = torch.where((tail.unsqueeze(2) == r.unsqueeze(1)).any(2), torch.full_like(tail, -1), tail)
+        cand = torch.cat([head, r_new, t_new], 1)
+        order = torch.argsort((cand < 0).to(torch.int8), dim=1, stable=True)[:, :gd]
+        F[s: s + step] = cand.gather(1, order).to(torch.int32)
+    return F
+
+
+def _cagra_search_host(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, seeds: torch.Tensor, k: int, itopk: int,
+                       width: int, max_iter: int, min_iter: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The search rule of ``cagra_search`` in torch, all queries of a chunk in step. A key is
+    (fp32 bits of d2) << 32 | id << 1 | expanded, as on the device."""
+    nq, n = Q.shape
+    N, gd = int(X.shape[0]), int(F.shape[1])
+    Xf, Fl = X.float(), F.long()
+    od = torch.full((nq, k), float("inf"), dtype=torch.float32)
+    oi = torch.full((nq, k), -1, dtype=torch.int64)
+    step = max(1, min(nq, (1 << 25) // max(1, N), (1 << 25) // max(1, max(width * gd, seeds.shape[1]) * n)))
+    for q0 in range(0, nq, step):
+        Qc = Q[q0: q0 + step].float()
+        m = Qc.shape[0]
+        rows = torch.arange(m).view(m, 1)
+        visited = torch.zeros((m, N), dtype=torch.bool)
+        keys = torch.full((m, itopk), _CAGRA_EMPTY, dtype=torch.int64)
+
+        def merge(keys: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+            cand = torch.where((cand >= 0) & (cand < N), cand, torch.full_like(cand, -1))
+            sc, order = torch.sort(cand, dim=1, stable=True)           # first of equal ids stays
+            dup = torch.zeros_like(sc, dtype=torch.bool)
+            dup[:, 1:] = sc[:, 1:] == sc[:, :-1]
+            first = torch.ones_like(dup).scatter_(1, order, ~dup)
+            new = (cand >= 0) & first & ~visited[rows, cand.clamp_min(0)]
+            visited[rows.expand_as(cand)[new], cand[new]] = True
+            d2 = ((Xf[cand.clamp_min(0)] - Qc.unsqueeze(1)) ** 2).sum(-1)
+            ck = (d2.contiguous().view(torch.int32).long() << 32) | (cand << 1)
+            ck = torch.where(new, ck, torch.full_like(ck, _CAGRA_EMPTY))
+            return torch.sort(torch.cat([keys, ck], 1), dim=1)[0][:, :itopk]
+
+        keys = merge(keys, seeds[q0: q0 + step].long())
+        for it in range(max_iter):
+            un = (keys != _CAGRA_EMPTY) & ((keys & 1) == 0)
+            pick = un & (torch.cumsum(un.long(), 1) <= width)
+            if not bool(pick.any()):
+                if it >= min_iter:
+                    break
+                continue
+            order = torch.argsort((~pick).to(torch.int8), dim=1, stable=True)[:, :width]
+            has = pick.gather(1, order)
+            par = torch.where(has, (keys.gather(1, order) & 0xFFFFFFFF) >> 1, torch.zeros_like(order))
+            keys = torch.where(pick, keys | 1, keys)
+            cand = torch.where(has.unsqueeze(2), Fl[par], torch.full((1,), -1, dtype=torch.int64)).view(m, -1)
+            keys = merge(keys, cand)
+        top = keys[:, :k]
+        ok = top != _CAGRA_EMPTY
+        od[q0: q0 + step] = torch.where(ok, (top >> 32).to(torch.int32).view(torch.float32),
+                                        torch.full((1,), float("inf")))
+        oi[q0: q0 + step] = torch.where(ok, (top & 0xFFFFFFFF) >> 1, torch.full_like(top, -1))
+    return od, oi
+
+
+def cagra_search(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, k: int, itopk: int = 64, width: int = 1,
+                 max_iter: int = 0, min_iter: int = 0, S: int = 64, seed: int = 1
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Greedy beam search of the fixed-degree graph ``F`` (int32 [N, gd], -1 padded) over the rows
+    ``X``: (d2 fp32 [nq, k] ascending, row positions int64 [nq, k]; empty slots +inf / -1).
+
+    Rule: a list of at most ``itopk`` entries (d2, id, expanded) ordered by (d2, id) and a visited
+    set V; a node enters V when it is first scored and is never scored again. Init: the
+    ``cagra_seeds(Q, N, S, seed)`` in slot order, duplicates dropped through V, scored, the best
+    itopk kept. Iteration ``t < max_iter``: the first ``width`` unexpanded entries in list order
+    (none and ``t >= min_iter``: stop) are marked expanded; their ``F`` rows, without -1 entries and
+    members of V, are scored and merged. ``d2 = sum (q - x)^2`` in fp32. ``max_iter = 0``:
+    ``cagra_auto_iters``. Device: ``srml_cagra_search_f32``, one workgroup per query with the list,
+    V and the query row in LDS (``cagra_lds_bytes``; past 160 KiB: ValueError); host: torch."""
+    nq, n = Q.shape
+    N = int(X.shape[0])
+    if X.dim() != 2 or X.shape[1] != n or n < 1:
+        raise ValueError("cagra_search: rows %s do not match %d query features" % (tuple(X.shape), n))
+    if F.dim() != 2 or F.dtype != torch.int32 or F.shape[0] != N:
+        raise ValueError("cagra_search: the graph must be int32 [%d, gd], got %s %s" % (N, F.dtype, tuple(F.shape)))
+    gd = int(F.shape[1])
+    max_iter = _cagra_check(n, gd, int(k), int(itopk), int(width), int(max_iter), int(min_iter), int(S))
+    od = torch.full((nq, k), float("inf"), dtype=torch.float32, device=Q.device)
+    oi = torch.full((nq, k), -1, dtype=torch.int64, device=Q.device)
+    if nq == 0 or N == 0:
+        return od, oi
+    seeds = cagra_seeds(Q, N, S, seed)
+    if not Q.is_cuda:
+        return _cagra_search_host(Q, X, F, seeds, int(k), int(itopk), int(width), max_iter, int(min_iter))
+    Qc = Q if Q.dtype == torch.float32 and Q.stride(1) == 1 else _c(Q.float())
+    Xc = X if X.dtype == torch.float32 and X.stride(1) == 1 else _c(X.float())
+    Fc = _c(F)
+    rc = native.call_status("srml_cagra_search_f32", Qc.data_ptr(), nq, n, Qc.stride(0), Xc.data_ptr(), N, Xc.stride(0),
+                            Fc.data_ptr(), gd, seeds.data_ptr(), int(S), int(k), int(itopk), int(width), max_iter,
+                            int(min_iter), od.data_ptr(), oi.data_ptr(), native.stream(Q.device))
+    if rc == -9:
+        raise ValueError("cagra_search: n=%d, itopk=%d, width=%d, graph degree=%d, seeds=%d, max_iter=%d do not fit "
+                         "the kernel's LDS" % (n, itopk, width, gd, S, max_iter))
+    if rc != 0:
+        raise RuntimeError("srml_cagra_search_f32 failed with status %d" % rc)
+    return od, oi
+
+
 def knn_lists_f16_ok(X: torch.Tensor, k: int, centroids: Optional[torch.Tensor]) -> bool:
     """The centred fp16 candidate kernel applies (n <= 128, n % 4 == 0, k <= 32, fp32 rows)."""
     return (KNN_LISTS_F16 and centroids is not None and X.is_cuda and X.dtype == torch.float32

@@ -31,7 +31,8 @@ _LONG_RESULT = ("srml_rf_bootstrap_ws", "srml_logreg_fold_ws", "srml_qn_mb_scrat
                 "srml_logreg_fold_parts", "srml_qn_args_size", "srml_logit_residual_ws", "srml_xtv_mfma_ws",
                 "srml_rf_partition_ws", "srml_dbscan_labels_ws", "srml_umap_categorical_ws",
                 "srml_umap_epoch_sync_ws",
-                "srml_label_sort_ws", "srml_radix_sort_ws", "srml_lloyd_moved_ws", "srml_sum_f32_ws", "srml_sum_sq_ws")
+                "srml_label_sort_ws", "srml_radix_sort_ws", "srml_lloyd_moved_ws", "srml_sum_f32_ws", "srml_sum_sq_ws",
+                "srml_cagra_lds_bytes")
 SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_col_moments_f32": (_P, _L, _I, _L, _P, _P, _P),
     "srml_col_moments_f64": (_P, _L, _I, _L, _P, _P, _P),
@@ -238,6 +239,11 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_pq_encode_f32": (_P, _L, _I, _L, _P, _I, _P, _P, _I, _I, _P, _P),
     "srml_ivfpq_search_f32": (_P, _L, _I, _L, _P, _I, _P, _I, _L, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P),
     "srml_ivfpq_candidates_f32": (_P, _L, _L, _I, _L, _P, _I, _P, _I, _L, _P, _P, _P, _I, _I, _I, _P, _P, _L, _P),
+    "srml_cagra_seeds_i32": (_P, _L, _I, _L, _L, _I, ctypes.c_uint, _P, _P),
+    "srml_cagra_prune_i32": (_P, _L, _I, _I, _P, _P),
+    "srml_cagra_merge_i32": (_P, _L, _I, _P, _P, _L, _P, _P),
+    "srml_cagra_lds_bytes": (_I, _I, _I, _I, _I, _I),
+    "srml_cagra_search_f32": (_P, _L, _I, _L, _P, _L, _L, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P),
 }
 
 _lock = threading.Lock()
