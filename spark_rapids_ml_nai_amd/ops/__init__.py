@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Any, Dict, Iterator, Optional, Tuple
+from typing import Any, Callable, Dict, Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1811,7 +1811,7 @@ def rf_predict(X: torch.Tensor, roots: torch.Tensor, feature: torch.Tensor, thre
 # ------------------------------------------------------------------------------------------
 # all-points IVF kNN candidates on fp16 MFMAs with query-list centring (ops.knn_lists centroids=)
 KNN_LISTS_F16 = os.environ.get("SRML_KNN_LISTS_F16", "1") != "0"
-KNN_KMAX = 64          # register/LDS insertion-list kernel (srml_knn_f32)
+KNN_KMAX = 64          # LDS insertion lists of the kNN / IVF / IVF-PQ kernels (csrc/neighbors.h NN_KMAX)
 TOPK_KMAX = 16384      # distance-chunk + radix-select path (srml_knn_dist_f32 + srml_topk_rows_f32)
 _TOPK_SLICE = 65536    # columns per select block
 _KNN_DIST_BYTES = 1 << 30  # distance chunk budget
@@ -2096,44 +2096,60 @@ def knn_metric(Q: torch.Tensor, I: torch.Tensor, k: int, metric: str, p: float =
 _IVF_CAND_BYTES = 1 << 30  # candidate matrix budget of the large-k IVF paths (distances + ids)
 
 
-def _ivf_large_k(Q: torch.Tensor, nq: int, probes: torch.Tensor, list_off: torch.Tensor, items: torch.Tensor,
-                 inorm: torch.Tensor, ids: Optional[torch.Tensor], k: int, qlist: Optional[torch.Tensor] = None
-                 ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """64 < k <= 1024 over IVF lists on the device: every (query, probe) writes its list's partial
-    distances ||i||^2 - 2 q.i (+ ids / list positions) into the query's candidate row
-    (``srml_ivf_candidates_f32``), then the radix-select kernel keeps k per row (ids carried).
-    Query chunks bound the candidate matrix to ``_IVF_CAND_BYTES``. Padding: +inf / -1."""
-    dev = Q.device
-    n = Q.shape[1]
-    st = native.stream(dev)
-    pr = _c(probes.int())
-    lo = _c(list_off.long())
-    ql = _c(qlist.int()) if qlist is not None else None
-    nprobe = int(pr.shape[1])
-    cmax = zeros(1, dtype=torch.int64, device=dev)
-    native.call("srml_ivf_candidate_max", pr.data_ptr(), nprobe, ql.data_ptr() if ql is not None else None, nq,
-                lo.data_ptr(), cmax.data_ptr(), st)
-    L = int(cmax.item())
+def _ivf_candidates_topk(nq: int, k: int, pr: torch.Tensor, lo: torch.Tensor, ql: Optional[torch.Tensor],
+                         launch: Callable[[int, int, torch.Tensor, torch.Tensor, int], None]
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """k > 64 over IVF lists on the device: ``launch(q0, r, D, DI, L)`` has every (query, probe) of
+    queries [q0, q0 + r) write its list's keys and ids / list positions into the query's row of the
+    candidate matrix D / DI (L columns, the largest candidate count), then the radix-select kernel
+    keeps k per row (ids carried). ``pr`` int32 probes, ``lo`` int64 list offsets, ``ql`` optional
+    int32 query -> probe row map, all contiguous. Query chunks bound the candidate matrix to
+    ``_IVF_CAND_BYTES``. Padding: +inf / -1."""
+    dev = pr.device
     od = torch.full((nq, k), float("inf"), dtype=torch.float32, device=dev)
     oi = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
-    if L == 0 or nq == 0:
+    nprobe = int(pr.shape[1])
+    if nq == 0 or nprobe == 0:
+        return od, oi
+    cmax = zeros(1, dtype=torch.int64, device=dev)
+    native.call("srml_ivf_candidate_max", pr.data_ptr(), nprobe, ql.data_ptr() if ql is not None else None, nq,
+                lo.data_ptr(), cmax.data_ptr(), native.stream(dev))
+    L = int(cmax.item())
+    if L == 0:
         return od, oi
     kk = min(k, L)
     R = max(1, min(nq, _IVF_CAND_BYTES // (L * 12)))
     D = torch.empty((R, L), dtype=torch.float32, device=dev)
     DI = torch.empty((R, L), dtype=torch.int64, device=dev)
-    Qc, Ic = _c(Q.float()), _c(items.float())
-    idc = _c(ids.long()) if ids is not None else None
-    inc = _c(inorm.float())
     for q0 in range(0, nq, R):
         r = min(R, nq - q0)
-        native.call("srml_ivf_candidates_f32", Qc.data_ptr(), q0, r, n, Qc.stride(0), pr.data_ptr(), nprobe,
-                    ql.data_ptr() if ql is not None else None, lo.data_ptr(), Ic.data_ptr(), Ic.stride(0),
-                    inc.data_ptr(), idc.data_ptr() if idc is not None else None, D.data_ptr(), DI.data_ptr(), L, st)
+        launch(q0, r, D, DI, L)
         v, i = topk_rows(D[:r], kk, ids=DI[:r])
         od[q0: q0 + r, :kk] = v
         oi[q0: q0 + r, :kk] = i
     return od, oi
+
+
+def _ivf_large_k(Q: torch.Tensor, nq: int, probes: torch.Tensor, list_off: torch.Tensor, items: torch.Tensor,
+                 inorm: torch.Tensor, ids: Optional[torch.Tensor], k: int, qlist: Optional[torch.Tensor] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """IVF-Flat candidates for ``_ivf_candidates_topk``: partial distances ||i||^2 - 2 q.i with the
+    items' ids, or their list positions without ``ids`` (``srml_ivf_candidates_f32``)."""
+    n = Q.shape[1]
+    st = native.stream(Q.device)
+    pr = _c(probes.int())
+    lo = _c(list_off.long())
+    ql = _c(qlist.int()) if qlist is not None else None
+    Qc, Ic = _c(Q.float()), _c(items.float())
+    idc = _c(ids.long()) if ids is not None else None
+    inc = _c(inorm.float())
+
+    def launch(q0: int, r: int, D: torch.Tensor, DI: torch.Tensor, L: int) -> None:
+        native.call("srml_ivf_candidates_f32", Qc.data_ptr(), q0, r, n, Qc.stride(0), pr.data_ptr(), int(pr.shape[1]),
+                    ql.data_ptr() if ql is not None else None, lo.data_ptr(), Ic.data_ptr(), Ic.stride(0),
+                    inc.data_ptr(), idc.data_ptr() if idc is not None else None, D.data_ptr(), DI.data_ptr(), L, st)
+
+    return _ivf_candidates_topk(nq, k, pr, lo, ql, launch)
 
 
 def ivf_search(Q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, items: torch.Tensor,
@@ -2232,39 +2248,6 @@ def pq_encode(X: torch.Tensor, codebooks: torch.Tensor, centroids: Optional[torc
     return codes
 
 
-def _ivfpq_large_k(Q: torch.Tensor, pr: torch.Tensor, lo: torch.Tensor, C: torch.Tensor, cbT: torch.Tensor,
-                   codes: torch.Tensor, M: int, ksub: int, k: int, ip: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """k > 64, as ``_ivf_large_k``: every (query, probe) writes its list's PQ keys and positions into
-    the query's candidate row (``srml_ivfpq_candidates_f32``); the radix-select kernel keeps k."""
-    dev = Q.device
-    nq, n = Q.shape
-    st = native.stream(dev)
-    nprobe = int(pr.shape[1])
-    od = torch.full((nq, k), float("inf"), dtype=torch.float32, device=dev)
-    oi = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
-    if nprobe == 0:
-        return od, oi
-    cmax = zeros(1, dtype=torch.int64, device=dev)
-    native.call("srml_ivf_candidate_max", pr.data_ptr(), nprobe, None, nq, lo.data_ptr(), cmax.data_ptr(), st)
-    L = int(cmax.item())
-    if L == 0:
-        return od, oi
-    kk = min(k, L)
-    R = max(1, min(nq, _IVF_CAND_BYTES // (L * 12)))
-    D = torch.empty((R, L), dtype=torch.float32, device=dev)
-    DI = torch.empty((R, L), dtype=torch.int64, device=dev)
-    for q0 in range(0, nq, R):
-        r = min(R, nq - q0)
-        rc = native.call_status("srml_ivfpq_candidates_f32", Q.data_ptr(), q0, r, n, Q.stride(0), pr.data_ptr(), nprobe,
-                                lo.data_ptr(), int(lo.shape[0]) - 1, int(codes.shape[0]), C.data_ptr(), cbT.data_ptr(),
-                                codes.data_ptr(), M, ksub, ip, D.data_ptr(), DI.data_ptr(), L, st)
-        _pq_refused("ivfpq_search", rc, n, M, ksub)
-        v, i = topk_rows(D[:r], kk, ids=DI[:r])
-        od[q0: q0 + r, :kk] = v
-        oi[q0: q0 + r, :kk] = i
-    return od, oi
-
-
 def ivfpq_search(Q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
                  codebooks: torch.Tensor, codes: torch.Tensor, k: int, inner_product: bool = False
                  ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2323,7 +2306,14 @@ def ivfpq_search(Q: torch.Tensor, probes: torch.Tensor, list_off: torch.Tensor, 
     cdc = _c(codes)
     ip = int(bool(inner_product))
     if k > KNN_KMAX:
-        return _ivfpq_large_k(Qc, pr, lo, C, cbT, cdc, M, ksub, k, ip)
+        def launch(q0: int, r: int, D: torch.Tensor, DI: torch.Tensor, L: int) -> None:
+            rc = native.call_status("srml_ivfpq_candidates_f32", Qc.data_ptr(), q0, r, n, Qc.stride(0), pr.data_ptr(),
+                                    int(pr.shape[1]), lo.data_ptr(), nlist, int(cdc.shape[0]), C.data_ptr(),
+                                    cbT.data_ptr(), cdc.data_ptr(), M, ksub, ip, D.data_ptr(), DI.data_ptr(), L,
+                                    native.stream(Q.device))
+            _pq_refused("ivfpq_search", rc, n, M, ksub)
+
+        return _ivf_candidates_topk(nq, k, pr, lo, None, launch)
     rc = native.call_status("srml_ivfpq_search_f32", Qc.data_ptr(), nq, n, Qc.stride(0), pr.data_ptr(),
                             int(pr.shape[1]), lo.data_ptr(), nlist, int(cdc.shape[0]), C.data_ptr(), cbT.data_ptr(),
                             cdc.data_ptr(), M, ksub, ip, k, od.data_ptr(), oi.data_ptr(), native.stream(Q.device))

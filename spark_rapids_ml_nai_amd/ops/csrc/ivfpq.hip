@@ -13,13 +13,15 @@
 // random codes sees about 3.5 distinct addresses on its busiest bank.
 #include "common.h"
 
+#include "neighbors.h"
+
 namespace {
+using namespace srml_nn;
 constexpr int PQ_T = 256;
-constexpr int PQ_KMAX = 64;    // per-wave sorted lists of the fused search kernel
 constexpr int PQ_MMAX = 128;
 constexpr int PQ_KSUBMAX = 256;
 // static LDS of the search kernel: 4 wave lists of (fp32 key, int64 position)
-constexpr size_t PQ_STATIC_LDS = 4 * PQ_KMAX * (sizeof(float) + sizeof(long long));
+constexpr size_t PQ_STATIC_LDS = sizeof(WaveD) + sizeof(WaveI);
 constexpr size_t PQ_LDS_TOTAL = 160 * 1024;  // per CU on gfx950; one workgroup may take all of it
 
 // The one place the dynamic LDS bytes of both scan kernels are computed: table | query residual.
@@ -90,17 +92,14 @@ __global__ __launch_bounds__(PQ_T) void ivfpq_search_kernel(const float* __restr
                                                             int ip, int vec, int k, float* __restrict__ out_d,
                                                             long long* __restrict__ out_i) {
   extern __shared__ __attribute__((aligned(16))) float pq_s[];  // lut [M * ksub] | qr [n]
-  __shared__ float wd[4][PQ_KMAX];
-  __shared__ long long wi[4][PQ_KMAX];
+  __shared__ WaveD wd;
+  __shared__ WaveI wi;
   float* lut = pq_s;
   float* qr = pq_s + M * ksub;
   const long q = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int dsub = n / M;
-  for (int j = t; j < 4 * PQ_KMAX; j += PQ_T) {
-    (&wd[0][0])[j] = __builtin_huge_valf();
-    (&wi[0][0])[j] = -1;
-  }
+  wave_lists_init(wd, wi);
   float thr = __builtin_huge_valf();
   bool have_lut = false;
   for (int p = 0; p < nprobe; ++p) {  // everything that steers this loop is block-uniform
@@ -131,36 +130,12 @@ __global__ __launch_bounds__(PQ_T) void ivfpq_search_kernel(const float* __restr
         const int g = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mask));
         mask &= mask - 1;
         const float dg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(key), g));
-        if (dg < thr) {
-          if (lane == 0) {
-            int pos = k - 1;
-            while (pos > 0 && wd[wid][pos - 1] > dg) {
-              wd[wid][pos] = wd[wid][pos - 1];
-              wi[wid][pos] = wi[wid][pos - 1];
-              --pos;
-            }
-            wd[wid][pos] = dg;
-            wi[wid][pos] = j0 + g;
-          }
-          __builtin_amdgcn_wave_barrier();
-          thr = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wd[wid][k - 1])));
-        }
+        if (dg < thr) wave_list_offer(wd, wi, k, dg, j0 + g, thr);
       }
     }
   }
   __syncthreads();
-  if (t == 0) {  // 4-way merge of the wave lists
-    int h[4] = {0, 0, 0, 0};
-    for (int j = 0; j < k; ++j) {
-      int bw = 0;
-      float bd = wd[0][h[0]];
-      for (int w = 1; w < 4; ++w)
-        if (wd[w][h[w]] < bd) { bd = wd[w][h[w]]; bw = w; }
-      out_d[q * k + j] = bd;
-      out_i[q * k + j] = bd < __builtin_huge_valf() ? wi[bw][h[bw]] : -1;
-      if (h[bw] < k - 1) ++h[bw]; else wd[bw][h[bw]] = __builtin_huge_valf();
-    }
-  }
+  if (t == 0) wave_lists_merge_write(wd, wi, k, out_d + q * k, out_i + q * k);
 }
 
 // One block per (query, probe), as ivf_candidates_kernel: the list's keys and positions go into
@@ -200,13 +175,6 @@ __global__ __launch_bounds__(PQ_T) void ivfpq_candidates_kernel(const float* __r
     drow[j - b0] = ip ? -(bias + a) : a;
     irow[j - b0] = j;
   }
-}
-
-__global__ void ivfpq_fill_kernel(float* __restrict__ D, long long* __restrict__ DI, long total) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  D[i] = __builtin_huge_valf();
-  DI[i] = -1;
 }
 
 // One wave per row: the row's residual sits in LDS, lanes split the codewords of one sub-space
@@ -277,7 +245,7 @@ SRML_API int srml_ivfpq_search_f32(const float* Q, long nq, int n, long ldq, con
                                    const unsigned char* codes, int M, int ksub, int ip, int k, float* out_d,
                                    long long* out_i, hipStream_t stream) {
   if (nq <= 0) return 0;
-  if (k < 1 || k > PQ_KMAX || nprobe < 0 || nq > 0x7fffffffL) return -8;
+  if (k < 1 || k > NN_KMAX || nprobe < 0 || nq > 0x7fffffffL) return -8;
   if (!pq_shape_ok(n, M, ksub)) return -9;
   const size_t lds = pq_lds_bytes(n, M, ksub);
   if (lds + PQ_STATIC_LDS > PQ_LDS_TOTAL) return -9;
@@ -300,8 +268,7 @@ SRML_API int srml_ivfpq_candidates_f32(const float* Q, long q0, long nq, int n, 
   if (!pq_shape_ok(n, M, ksub)) return -9;
   const size_t lds = pq_lds_bytes(n, M, ksub);
   if (lds > PQ_LDS_TOTAL) return -9;
-  const long total = nq * ldd;
-  hipLaunchKernelGGL(ivfpq_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, D, DI, total);
+  srml_nn::fill_candidates(D, DI, nq * ldd, stream);
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)ivfpq_candidates_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);

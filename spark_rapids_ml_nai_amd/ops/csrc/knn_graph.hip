@@ -16,11 +16,10 @@
 // on one XCD and share its L2. Output positions are row indices in the sorted (list) order.
 #include "common.h"
 
-#include "tile.h"
+#include "neighbors.h"
 
 namespace {
-using namespace srml_tile;
-constexpr int KG_KMAX = 64;
+using namespace srml_nn;
 
 template <bool VEC>
 __global__ __launch_bounds__(256, 1) void knn_lists_kernel(const float* __restrict__ X, int n, long ld,
@@ -39,8 +38,8 @@ __global__ __launch_bounds__(256, 1) void knn_lists_kernel(const float* __restri
     float D[BM][BN + 1];
   };
   __shared__ Smem sm;
-  __shared__ float topd[BM][KG_KMAX + 1];
-  __shared__ int topi[BM][KG_KMAX + 1];
+  __shared__ float topd[BM][NN_KMAX + 1];
+  __shared__ int topi[BM][NN_KMAX + 1];
   const int b = xcd_remap(blockIdx.x, gridDim.x);
   if (b >= ntiles) return;  // block-uniform
   const int c = tile_list[b];
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(256, 1) void knn_lists_kernel(const float* __restri
   const int lane = t & 63, wid = t >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int lk = lane >> 5, li = lane & 31;
-  for (int i = t; i < BM * (KG_KMAX + 1); i += 256) {
+  for (int i = t; i < BM * (NN_KMAX + 1); i += 256) {
     (&topd[0][0])[i] = __builtin_huge_valf();
     (&topi[0][0])[i] = -1;
   }
@@ -157,7 +156,7 @@ SRML_API int srml_knn_lists_f32(const float* X, int n, long ld, const float* xno
                                 const int* probes, int nprobe, const long long* tile_q0, const int* tile_list,
                                 int ntiles, int k, float* out_d, int* out_i, hipStream_t stream) {
   if (ntiles <= 0) return 0;
-  if (k < 1 || k > KG_KMAX) return -8;
+  if (k < 1 || k > NN_KMAX) return -8;
   const bool vec = ((ld & 3) == 0) && ((n & 3) == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
   if (vec)
     hipLaunchKernelGGL(knn_lists_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, stream, X, n, ld, xnorm, list_off,

@@ -1,6 +1,6 @@
-"""The kNN-graph builders (models/knn_graph.py; knn_graph.hip, topk.hip, group.hip, the fp16
-bucketing of splitmm.hip) at their edges: k below the NN-descent fan-out, rows with fewer than k
-reachable candidates (padded with -1), centres outside the range an fp16 plane was scaled for, and
+"""The kNN-graph builders (models/knn_graph.py; knn_graph.hip, knn.hip, ivf.hip, topk.hip,
+group.hip, the fp16 bucketing of splitmm.hip) at their edges: k below the NN-descent fan-out, rows
+with fewer than k reachable candidates (padded with -1), centres outside the range an fp16 plane was scaled for, and
 padded graphs through the fuzzy-set kernels that consume them.
 
 Every oracle is plain numpy / torch in fp64, written here, and calls none of the code under test.
