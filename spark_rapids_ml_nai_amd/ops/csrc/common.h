@@ -101,6 +101,25 @@ __device__ __forceinline__ void logistic_terms(double z, double y, double& res, 
   loss = (z > 0.0 ? z : 0.0) - y * z + (double)log1pf(e);
 }
 
+// The same terms evaluated in fp64, for the kernels fed fp64 data (float32_inputs=False): exp / log1p
+// in double, and the residual formed as (1 - y) - q for z >= 0 and q - y below, q = e / (1 + e), so a
+// saturated, correctly classified row keeps -e^-|z| to relative accuracy where the fp32 sigmoid
+// rounds to exactly 0 or 1 (an absolute error of ~6e-8 per row, eight digits short of the fp64
+// softmax path).
+__device__ __forceinline__ void logistic_terms_f64(double z, double y, double& res, double& loss) {
+  const double e = exp(-fabs(z));  // in (0, 1]
+  const double q = e / (1.0 + e);
+  res = z >= 0.0 ? (1.0 - y) - q : q - y;
+  loss = (z > 0.0 ? z : 0.0) - y * z + log1p(e);
+}
+
+// The terms at the precision of the kernel's value type T: fp32 data keeps the fast fp32 evaluation.
+template <typename T>
+__device__ __forceinline__ void logistic_terms_as(double z, double y, double& res, double& loss) {
+  if constexpr (sizeof(T) == sizeof(double)) logistic_terms_f64(z, y, res, loss);
+  else logistic_terms(z, y, res, loss);
+}
+
 static inline int srml_status() { return (int)hipGetLastError(); }
 
 // An AMD dispatch packet carries the grid size in WORK-ITEMS as a 32-bit field: blocks * threads

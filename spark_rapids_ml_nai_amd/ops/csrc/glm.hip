@@ -436,9 +436,12 @@ __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restr
                                                             long rows_per_block) {
   if (flag && *flag) return;  // the on-device quasi-Newton driver has converged
   const double b = bptr ? *bptr : b_in;
-  // w is kept in fp64 (LDS) and margins / losses are evaluated in fp64 so that the objective the
-  // quasi-Newton line search sees is smooth to ~1e-15; X stays fp32 and the kernel stays
-  // HBM-bound (fp64 FMA rate is far above the 1 FMA per 4 streamed bytes needed here).
+  // w is kept in fp64 (LDS) and the margins and the piecewise-linear part of the loss are evaluated
+  // in fp64; the sigmoid and log1p(exp(-|z|)) go through the fp32 hardware exp / log
+  // (logistic_terms), so each row's residual and loss term carry an absolute error of ~6e-8 (a few
+  // fp32 ulps of a value in [0, 1]), summed in fp64: that, not 1e-15, is what the quasi-Newton line
+  // search sees on the fp32 paths. X stays fp32 and the kernel stays HBM-bound (fp64 FMA rate is far
+  // above the 1 FMA per 4 streamed bytes needed here).
   extern __shared__ __attribute__((aligned(16))) double ldsd[];  // w[256*V] (fp64) then gsum[256*V] (fp32)
   double* ws = ldsd;
   float* gs = reinterpret_cast<float*>(ldsd + 256 * V);

@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256) void logit_residual_kernel(const TZ* __restric
       for (int k = 0; k < KB; ++k) {
         if (k < K) {
           double res, l;
-          logistic_terms(z[k], (double)yr, res, l);
+          logistic_terms_as<TZ>(z[k], (double)yr, res, l);
           if (zmode != 1) R[r * ldr + k] = (TZ)res;
           sg[k] += res;
           sls[k] += l;
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(256) void logreg_binary_lds_kernel(const T* __restr
     for (int c = lane; c < n; c += 64) dot = fma((double)row[c], w[c], dot);
     dot = wave_sum(dot);
     double res, lt;
-    logistic_terms(dot + b, (double)y[r], res, lt);
+    logistic_terms_as<T>(dot + b, (double)y[r], res, lt);
     if (lane == 0) {
       gb += res;
       loss += lt;

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void csr_logreg_binary_kernel(const long* __re
     for (long p = p0 + CACHE * G + l; p < p1; p += G) dot = fma((double)data[p], w[indices[p]], dot);
     dot = group_sum<G>(dot);
     double res, lt;
-    logistic_terms(dot + b, (double)y[r], res, lt);
+    logistic_terms_as<T>(dot + b, (double)y[r], res, lt);
     if (l == 0) {
       gb += res;
       loss += lt;
