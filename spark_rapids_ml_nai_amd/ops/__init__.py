@@ -449,19 +449,20 @@ def split_bf16x3(X: torch.Tensor, row_multiple: int = 128, tiled: bool = False,
 CERTIFY_TAU = 2.0 ** -13  # dropped-product bound of the 3-product search (3 * 2^-16, 8x slack), per ||x|| ||c||
 
 
-def split_bf16x3_rows(X: torch.Tensor, rows: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+def split_bf16x3_rows(X: torch.Tensor, rows: torch.Tensor, mu: Optional[torch.Tensor]) -> torch.Tensor:
     """``split_bf16x3(X[rows], tiled=True, mu=mu)`` without the gathered copy of the rows
-    (``srml_split_bf16x3_tiled_centered_rows`` reads them through the index list)."""
+    (``srml_split_bf16x3_tiled_centered_rows`` reads them through the index list; ``mu`` None:
+    planes of the rows themselves, as the certified search on uncentred planes re-searches them)."""
     m, n = int(rows.shape[0]), X.shape[1]
     if not X.is_cuda or X.dtype != torch.float32 or X.stride(1) != 1:
         return split_bf16x3(X.index_select(0, rows.long()), tiled=True, mu=mu)
     kp = (n + 15) // 16 * 16
     rows_pad = max(256, (m + 255) // 256 * 256)
     P = torch.empty((3, rows_pad // 256, kp // 16, 256, 16), dtype=torch.bfloat16, device=X.device)
-    muf = _c(mu.float().view(-1))
+    muf = _c(mu.float().view(-1)) if mu is not None else None
     ri = _c(rows.to(torch.int32))
     native.call("srml_split_bf16x3_tiled_centered_rows", X.data_ptr(), X.stride(0), ri.data_ptr(), m, n,
-                muf.data_ptr(), kp, rows_pad, P.data_ptr(), native.stream(X.device))
+                muf.data_ptr() if muf is not None else None, kp, rows_pad, P.data_ptr(), native.stream(X.device))
     return P
 
 
