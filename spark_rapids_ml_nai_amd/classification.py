@@ -335,6 +335,238 @@ class LogisticRegressionModel(LogisticRegressionClass, _ModelWithPredictionCol, 
 
 
 # ======================================================================================
+# LinearSVC
+# ======================================================================================
+class LinearSVCClass(_BackendClass):
+    @classmethod
+    def _param_mapping(cls) -> Dict[str, Optional[str]]:
+        return {
+            "maxIter": "max_iter",
+            "regParam": "C",
+            "tol": "tol",
+            "fitIntercept": "fit_intercept",
+            "standardization": "standardization",
+            "weightCol": None,
+            "aggregationDepth": None,
+            "maxBlockSizeInMB": None,
+        }  # threshold is a model-side Param (the cut on the margin): no backend kwarg mirrors it
+
+    @classmethod
+    def _param_value_mapping(cls) -> Dict[str, Callable[[Any], Any]]:
+        return {"C": lambda x: 1 / x if x > 0.0 else (0.0 if x == 0.0 else None)}
+
+    def _get_backend_params_default(self) -> Dict[str, Any]:
+        return {"fit_intercept": True, "standardization": True, "verbose": False, "C": 0.0, "penalty": "l2",
+                "loss": "hinge", "max_iter": 100, "tol": 1e-6}
+
+
+_SVC_LOSSES = ("hinge", "squared_hinge")
+
+
+class _LinearSVCParams(_BackendParams, HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredictionCol,
+                       HasRawPredictionCol, HasMaxIter, HasRegParam, HasTol, HasFitIntercept, HasStandardization,
+                       HasWeightCol, HasAggregationDepth, HasMaxBlockSizeInMB, HasEnableSparseDataOptim,
+                       _FeaturesColMixin):
+    # Spark's LinearSVC declares its own threshold: a cut on the margin, not a probability
+    threshold = Param(Params._dummy(), "threshold",
+                      "The threshold in binary classification applied to the linear model prediction. This threshold "
+                      "can be any real number, where Inf will make all predictions 0.0 and -Inf will make all "
+                      "predictions 1.0.", typeConverter=TypeConverters.toFloat)
+
+    def __init__(self) -> None:
+        super().__init__()
+        self._setDefault(maxIter=100, regParam=0.0, tol=1e-6, fitIntercept=True, standardization=True, threshold=0.0,
+                         aggregationDepth=2, maxBlockSizeInMB=0.0, featuresCol="features", labelCol="label",
+                         predictionCol="prediction", rawPredictionCol="rawPrediction")
+
+    def setRawPredictionCol(self, value: str) -> Any:
+        return self._set(rawPredictionCol=value)
+
+    def getThreshold(self) -> float:
+        return self.getOrDefault("threshold")
+
+    def setThreshold(self, value: float) -> Any:
+        """Decision threshold on the margin w.x + b (any real number; Spark's default 0.0)."""
+        return self._set(threshold=float(value))
+
+    def _set_params(self, **kwargs: Any) -> Any:
+        if "loss" in kwargs and kwargs["loss"] not in _SVC_LOSSES:
+            raise ValueError(f"loss must be 'hinge' or 'squared_hinge', got {kwargs['loss']!r}")
+        return super()._set_params(**kwargs)
+
+
+class LinearSVC(LinearSVCClass, _EstimatorSupervised, _LinearSVCParams):
+    """Distributed linear support-vector classifier: Spark's hinge loss (``loss="hinge"``, strict
+    kink) or cuML's squared hinge (``loss="squared_hinge"``), L2 penalty, on the fused one-pass
+    loss/gradient HIP kernels and the device-resident L-BFGS of ``LogisticRegression``."""
+
+    @keyword_only
+    def __init__(self, *, featuresCol: Union[str, List[str]] = "features", labelCol: str = "label",
+                 predictionCol: str = "prediction", rawPredictionCol: str = "rawPrediction", maxIter: int = 100,
+                 regParam: float = 0.0, tol: float = 1e-6, fitIntercept: bool = True, standardization: bool = True,
+                 threshold: float = 0.0, loss: str = "hinge", enable_sparse_data_optim: Optional[bool] = None,
+                 float32_inputs: bool = True, num_workers: Optional[int] = None,
+                 verbose: Union[int, bool] = False, **kwargs: Any) -> None:
+        super().__init__()
+        self._set_params(**self._input_kwargs)
+
+    def setMaxIter(self, value: int) -> "LinearSVC":
+        return self._set_params(maxIter=value)
+
+    def setRegParam(self, value: float) -> "LinearSVC":
+        return self._set_params(regParam=value)
+
+    def setTol(self, value: float) -> "LinearSVC":
+        return self._set_params(tol=value)
+
+    def setFitIntercept(self, value: bool) -> "LinearSVC":
+        return self._set_params(fitIntercept=value)
+
+    def setStandardization(self, value: bool) -> "LinearSVC":
+        return self._set_params(standardization=value)
+
+    def _supports_sparse(self) -> bool:
+        return True
+
+    def _enable_fit_multiple_in_single_pass(self) -> bool:
+        return True
+
+    def _supportsTransformEvaluate(self, evaluator: Any) -> bool:
+        if type(evaluator).__name__ != "MulticlassClassificationEvaluator":
+            return False
+        return evaluator.getMetricName() in (
+            "f1", "accuracy", "weightedPrecision", "weightedRecall", "weightedTruePositiveRate",
+            "weightedFalsePositiveRate", "weightedFMeasure", "truePositiveRateByLabel", "falsePositiveRateByLabel",
+            "precisionByLabel", "recallByLabel", "fMeasureByLabel", "hammingLoss")
+
+    def _validate_parameters(self) -> None:
+        if self.isSet("weightCol") and self.getOrDefault("weightCol"):
+            raise ValueError("weightCol is not supported")
+        if self._backend_params.get("loss") not in _SVC_LOSSES:
+            raise ValueError(f"loss must be 'hinge' or 'squared_hinge', got {self._backend_params.get('loss')!r}")
+
+    def _get_fit_func(self, dataset: DataFrame, extra_params: Optional[List[Dict[str, Any]]] = None) -> Callable:
+        def _fit(inp: FitInput, ctx: WorkerContext, params: Dict[str, Any]) -> Any:
+            from .core.base import CSR
+            from .models.svc import svc_fit, svc_stats
+
+            sparse = isinstance(inp.X, CSR)
+            stats = svc_stats(inp.X, inp.y, inp.desc.m, ctx, sparse)  # one ingest, one stats pass
+            init = params["cuml_init"]
+            out = []
+            for mp in params["fit_multiple_params"] or [{}]:  # the param maps, one after another
+                p = dict(init, **mp)
+                C = float(p["C"])
+                out.append(svc_fit(inp.X, inp.y, inp.desc.m, ctx, 0.0 if C == 0.0 else 1.0 / C,
+                                   bool(p["fit_intercept"]), bool(p["standardization"]), int(p["max_iter"]),
+                                   float(p["tol"]), loss=str(p["loss"]), sparse=sparse, stats=stats))
+            return out if params["fit_multiple_params"] else out[0]
+
+        return _fit
+
+    def _create_model(self, result: Dict[str, Any]) -> "LinearSVCModel":
+        result = dict(result)
+        info = result.pop("_solver", None)  # device QN diagnostics (evaluations, stop reason, pass)
+        model = LinearSVCModel._from_row(result)
+        model._solver_info = info
+        return model
+
+
+class LinearSVCModel(LinearSVCClass, _ModelWithPredictionCol, _LinearSVCParams):
+    def __init__(self, coef_: List[float], intercept_: float, n_cols: int, dtype: str, num_iters: int = 0,
+                 objective: float = 0.0) -> None:
+        super().__init__(coef_=coef_, intercept_=intercept_, n_cols=n_cols, dtype=dtype, num_iters=num_iters,
+                         objective=objective)
+        self.coef_ = coef_
+        self.intercept_ = intercept_
+        self.n_cols = n_cols
+        self.dtype = dtype
+        self.num_iters = num_iters
+        self.objective = objective
+
+    @property
+    def coefficients(self) -> Any:
+        return Vectors.dense(self.coef_)
+
+    @property
+    def intercept(self) -> float:
+        return float(self.intercept_)
+
+    @property
+    def numClasses(self) -> int:
+        return 2
+
+    @property
+    def hasSummary(self) -> bool:
+        return False
+
+    @property
+    def summary(self) -> Any:
+        raise RuntimeError("No training summary available for this LinearSVCModel")
+
+    def _margin_np(self, value: Any) -> float:
+        x = as_dense_array(value).reshape(-1)
+        return float(x @ np.asarray(self.coef_, dtype=np.float64) + float(self.intercept_))
+
+    def predictRaw(self, value: Any) -> Any:
+        z = self._margin_np(value)
+        return Vectors.dense([-z, z])
+
+    def predict(self, value: Any) -> float:
+        return 1.0 if self._margin_np(value) > float(self.getOrDefault("threshold")) else 0.0
+
+    def evaluate(self, dataset: Any) -> Any:
+        raise NotImplementedError("evaluate() summaries are not supported; use an Evaluator on transform()")
+
+    def cpu(self) -> Any:
+        from .utils.spark_compat import to_spark_linear_svc_model
+
+        return to_spark_linear_svc_model(self)
+
+    def _vector_output_cols(self) -> List[str]:
+        return [self.getOrDefault("rawPredictionCol")]
+
+    def _transform_supports_sparse(self) -> bool:
+        return True
+
+    def _get_transform_func(self, dataset: DataFrame) -> Tuple[Callable, Callable]:
+        W = np.asarray(self.coef_, dtype=np.float64).reshape(1, -1)
+        b = np.asarray([self.intercept_], dtype=np.float64)
+        pc, rc = self.getPredictionCol(), self.getOrDefault("rawPredictionCol")
+        thr = float(self.getOrDefault("threshold"))
+        np_dt = np.float32 if self.dtype == "float32" else np.float64
+
+        def construct(ctx: WorkerContext) -> Tuple[torch.Tensor, torch.Tensor]:
+            return torch.from_numpy(W.astype(np_dt)).to(ctx.device), torch.from_numpy(b.astype(np_dt)).to(ctx.device)
+
+        def predict(state: Tuple[torch.Tensor, torch.Tensor], X: Any, ctx: WorkerContext) -> Dict[str, np.ndarray]:
+            from .core.base import CSR, to_device
+            from .models.logistic import logistic_scores
+
+            Wd, bd = state
+            Xd = to_device(X, ctx.device, Wd.dtype)
+            if isinstance(Xd, CSR):
+                from . import ops
+
+                S = ops.csr_spmm(Xd, Wd.T, bd)
+            else:
+                S = logistic_scores(Xd, Wd, bd)
+            z = S.double()[:, 0]
+            return {pc: ctx.output((z > thr).double()), rc: ctx.output(torch.stack([-z, z], 1))}
+
+        return construct, predict
+
+    @classmethod
+    def _combine(cls, models: List["LinearSVCModel"]) -> "LinearSVCModel":
+        first = models[0]
+        out = cls(**first._get_model_attributes())
+        first._copyValues(out)
+        first._copy_backend_params(out)
+        out._combined_models = list(models)
+        return out
+
+
+# ======================================================================================
 # RandomForestClassifier
 # ======================================================================================
 from .tree import _RandomForestEstimator, _RandomForestModel  # noqa: E402

@@ -845,7 +845,8 @@ def _eval_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> List[List[Any]
                 if kind == "regression":
                     row.append(RegressionSummary.from_moments(len(y), ops.reg_moments(yd, p)))
                     continue
-                prob = res.get(m.getOrDefault("probabilityCol"))
+                # (a margin classifier such as LinearSVC has no probability column)
+                prob = res.get(m.getOrDefault("probabilityCol")) if m.hasParam("probabilityCol") else None
                 width = int(prob.shape[1]) if isinstance(prob, torch.Tensor) and prob.dim() == 2 else 0
                 finite = bool(np.isfinite(y).all()) if len(y) else True
                 C = max(width, int(y.max()) + 1 if len(y) and finite else 1, 1)

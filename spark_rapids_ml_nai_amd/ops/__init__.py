@@ -16,7 +16,7 @@ from ..utils.determinism import deterministic
 
 __all__ = ["col_moments", "gram", "xw", "dgemm", "sign_flip", "is_native", "xtv", "row_sqnorm",
            "logreg_binary_loss_grad", "nearest_centroid", "cluster_sums", "csr_logreg_binary_loss_grad",
-           "csr_spmm", "csr_spmtm", "csr_col_moments", "logistic_loss_grad"]
+           "csr_spmm", "csr_spmtm", "csr_col_moments", "logistic_loss_grad", "svc_path", "svc_loss_grad"]
 
 
 def is_native(t: torch.Tensor) -> bool:
@@ -3768,6 +3768,159 @@ def logistic_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, K
                       zc=zcache if path == "two_pass_multinomial_f32" else None)
     elif path == "two_pass_deterministic_f32":  # binary: one sigmoid model
         _glm_two_pass(X, y32, w.view(1, n), b, 1, 1, out, 1, n, out[n:], 1, out[n + 1:], 1, flag)
+    else:  # pragma: no cover
+        raise AssertionError(path)
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# LinearSVC (hinge / squared hinge) data term: the binary logistic kernels with another loss policy
+SVC_LOSSES = {"hinge": 0, "squared_hinge": 1}
+
+
+def svc_path(X) -> str:
+    """Which pass ``svc_loss_grad`` uses for X (reported by the fit / asserted in tests)."""
+    if _is_csr(X):
+        return "csr_svc" if X.data.is_cuda else "torch-cpu"
+    if not X.is_cuda:
+        return "torch-cpu"
+    n = X.shape[1]
+    f32 = X.dtype == torch.float32
+    if deterministic() and f32:
+        return "two_pass_deterministic_svc_f32"
+    if f32 and n <= 4096:
+        return "fused_svc_f32"
+    if X.dtype in (torch.float32, torch.float64) and n <= 16384:
+        return "lds_svc_" + ("f32" if f32 else "f64")
+    return "two_pass_svc_f32" if f32 else "two_pass_svc_f64"
+
+
+def exact_sum(T: torch.Tensor, bound: Any, dim: int = 0) -> torch.Tensor:
+    """Sum of the fp64 terms T over ``dim`` on a fixed-point grid: every term is rounded to a multiple
+    of 2^(e - 52), 2^e > ``bound`` >= the magnitude of ANY partial sum of the terms (over all rows of
+    all ranks), so every addition is exact and the result does not depend on the order of the sum,
+    on how the rows are split over ranks, or on the all-reduce that adds the ranks' sums. Each term
+    moves by at most 2^(e - 53). e is the binary exponent of ``bound`` (``frexp``: bound = f 2^e,
+    0.5 <= f < 1, no logarithm to round), so partial sums are integers below 2^52 on the grid; the
+    terms' own rounding and a bound rounded down in its last place fit in the bit that fp64 has
+    above that. ``bound`` (scalar or one per kept column) must be the same everywhere: build it from
+    all-reduced maxima and ``math.fsum``. Costs a temporary of T's size."""
+    bound = torch.as_tensor(bound, dtype=torch.float64, device=T.device).clamp_min(2.0 ** -900)
+    grid = torch.ldexp(torch.ones_like(bound), torch.frexp(bound).exponent - 52)
+    return (torch.round(T / grid) * grid).sum(dim)
+
+
+def _svc_exact_cpu(Xd: torch.Tensor, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor, kind: int,
+                   xmax: torch.Tensor, m_total: float) -> torch.Tensor:
+    """The ``torch-cpu`` data term with every sum on ``exact_sum``'s grid (deterministic mode): the
+    margins, the gradient columns, the bias gradient and the loss are bit-identical however the
+    rows are split over ranks. ``xmax`` (n): max |x| per column over all ranks' rows. Two m x n fp64
+    temporaries per evaluation (the caller densifies CSR input): the price of the mode on the host
+    reference path."""
+    n = Xd.shape[1]
+    wd, b0 = w.double().view(-1), float(b.double().view(-1)[0])
+    bz = math.fsum((xmax * wd.abs()).tolist())  # >= |x_r . w| on every row; fsum: correctly rounded
+    z = exact_sum(Xd * wd.view(1, n), bz, 1) + b0
+    s = 2.0 * y32.double() - 1.0
+    h = 1.0 - s * z
+    act = (h > 0).double()  # strict: the kink is inactive
+    hb = 2.0 + bz + abs(b0)  # >= |h| on every row
+    r = -2.0 * s * h * act if kind else -s * act
+    rb = 2.0 * hb if kind else 1.0
+    out[:n] += exact_sum(Xd * r.view(-1, 1), m_total * rb * xmax)
+    out[n] += exact_sum(r, m_total * rb)
+    out[n + 1] += exact_sum(h * h * act if kind else h * act, m_total * (hb * hb if kind else hb))
+    return out
+
+
+def svc_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor,
+                  flag: Optional[torch.Tensor] = None, loss: str = "hinge", ws: Optional[torch.Tensor] = None,
+                  leave_partials: bool = False, exact: Optional[tuple] = None) -> torch.Tensor:
+    """ADD the summed support-vector data term at (w, b) into ``out`` = [grad w (n) | grad b | loss
+    sum] (fp64). Labels 0/1, y' = 2y - 1, z = x.w + b: ``hinge`` max(0, 1 - y'z) (residual -y' where
+    1 - y'z > 0, strictly: a row on the kink contributes nothing, as Spark's HingeAggregator) or
+    ``squared_hinge`` max(0, 1 - y'z)^2 (residual -2 y' max(0, 1 - y'z)). ``w`` (n), ``b`` (1) are
+    fp64 tensors read on the device; ``flag`` / ``ws`` / ``leave_partials`` as ``logistic_loss_grad``
+    (the partial-row workspace is ``logreg_workspace(X)``: same grid). X: dense (m, n) or CSR.
+    ``exact`` = (max |x| per column over all ranks (n, fp64), total rows), ``torch-cpu`` only: the
+    sums run on ``exact_sum``'s fixed-point grid, so ranks' sums add up to the one-rank sum bit for
+    bit (the deterministic mode of a distributed fit)."""
+    if loss not in SVC_LOSSES:
+        raise ValueError(f"loss must be 'hinge' or 'squared_hinge', got {loss!r}")
+    kind = SVC_LOSSES[loss]
+    path = svc_path(X)
+    csr = _is_csr(X)
+    if csr:
+        m, n = X.shape
+        dev = X.data.device
+    else:
+        # the fused and LDS kernels take a row stride: a row-strided view (unit column stride) is
+        # read in place; the two-pass products want a dense matrix, and a partial-row workspace
+        # (logreg_workspace) is sized for the dense copy
+        if not (X.dim() == 2 and X.stride(1) == 1 and X.stride(0) >= X.shape[1] and ws is None
+                and (path == "fused_svc_f32" or path.startswith("lds_svc"))):
+            X = _c(X)
+        m, n = X.shape
+        dev = X.device
+    if path == "torch-cpu":
+        wd = w.double().view(n, 1)
+        if csr:
+            Xd = _csr_torch(X)
+            Xd = Xd.to(torch.float64) if Xd.dtype != torch.float64 else Xd
+        else:
+            Xd = X.double()
+        if exact is not None:
+            return _svc_exact_cpu(Xd.to_dense() if csr else Xd, y32, w, b, out, kind, exact[0], float(exact[1]))
+        z = (Xd @ wd).view(-1) + b.double().view(-1)[0]
+        s = 2.0 * y32.double() - 1.0
+        h = 1.0 - s * z
+        act = (h > 0).double()  # strict: the kink is inactive
+        r = -2.0 * s * h * act if kind else -s * act
+        lsum = (h * h * act).sum() if kind else (h * act).sum()
+        out[:n] += (Xd.t() @ r.view(-1, 1)).view(-1)
+        out[n] += r.sum()
+        out[n + 1] += lsum
+        return out
+    st = native.stream(dev)
+    fp = flag.data_ptr() if flag is not None else None
+    assert w.dtype == torch.float64 and b.dtype == torch.float64 and out.dtype == torch.float64
+    assert w.numel() == n and b.numel() == 1 and out.numel() == n + 2 and y32.dtype == torch.float32
+    if path == "csr_svc":
+        _csr_check(X)
+        native.call("srml_csr_svc_loss_grad_" + _sfx(X), X.indptr.data_ptr(), X.indices.data_ptr(), X.data.data_ptr(),
+                    m, n, X.data.numel(), y32.data_ptr(), w.data_ptr(), 0.0, b.data_ptr(), fp, out.data_ptr(), kind, st)
+    elif path == "fused_svc_f32":
+        native.call("srml_svc_loss_grad_f32", X.data_ptr(), m, n, X.stride(0), y32.data_ptr(), w.data_ptr(), 0.0,
+                    b.data_ptr(), fp, out.data_ptr(), ws.data_ptr() if ws is not None else None,
+                    int(bool(leave_partials and ws is not None)), kind, st)
+    elif path.startswith("lds_svc"):
+        native.call("srml_svc_loss_grad_lds_" + path[-3:], X.data_ptr(), m, n, X.stride(0), y32.data_ptr(),
+                    w.data_ptr(), 0.0, b.data_ptr(), fp, out.data_ptr(), kind, st)
+    elif path == "two_pass_svc_f64":
+        # margins and X^T r on the fp64 MFMA GEMM around the fp64 residual kernel
+        z = dgemm(X, w.view(n, 1))
+        r = zeros((m, 1), dtype=torch.float64, device=dev)  # stays 0 if the done flag skips it
+        native.call("srml_svc_residual_f64", z.data_ptr(), m, 1, 1, y32.data_ptr(), b.data_ptr(), 1, 1,
+                    r.data_ptr(), 1, out[n:].data_ptr(), 1, out[n + 1:].data_ptr(), 1, fp, kind, st)
+        dgemm(X, r, ta=True, beta=1.0, out=out[:n].view(n, 1))
+    elif path in ("two_pass_svc_f32", "two_pass_deterministic_svc_f32"):
+        # margins (srml_xw_f32), the residual kernel, then grad += X^T r (srml_xtv2_f32; ordered
+        # block-row partials on srml_xtv_mfma_det_f32 in deterministic mode)
+        Z = xw(X, w.view(n, 1).float().contiguous())
+        R = torch.empty((m, 1), dtype=torch.float32, device=dev)  # the X^T r pass skips on the flag too
+        args =(Z.data_ptr(), m, 1, Z.stride(0), y32.data_ptr(), b.data_ptr(), 1, 1, R.data_ptr(), 1,
+                out[n:].data_ptr(), 1, out[n + 1:].data_ptr(), 1, fp)
+        if path == "two_pass_deterministic_svc_f32":
+            L = native.lib()
+            dws = torch.empty(max(int(L.srml_logit_residual_ws(m, 1)), int(L.srml_xtv_mfma_ws(m, n, 1)), 1),
+                              dtype=torch.float64, device=dev)
+            native.call("srml_svc_residual_det_f32", *args, dws.data_ptr(), kind, st)
+            native.call("srml_xtv_mfma_det_f32", X.data_ptr(), m, n, X.stride(0), R.data_ptr(), 1, 1, out.data_ptr(),
+                        1, n, fp, dws.data_ptr(), st)
+        else:
+            native.call("srml_svc_residual_f32", *args, kind, st)
+            native.call("srml_xtv2_f32", X.data_ptr(), m, n, X.stride(0), R.data_ptr(), 1, 1, out.data_ptr(), 1, n,
+                        fp, st)
     else:  # pragma: no cover
         raise AssertionError(path)
     return out

@@ -120,6 +120,39 @@ __device__ __forceinline__ void logistic_terms_as(double z, double y, double& re
   else logistic_terms(z, y, res, loss);
 }
 
+// Per-row support-vector terms (LinearSVC), labels y in {0, 1}: with s = 2 y - 1 and the hinge
+// h = 1 - s z, loss = max(0, h) (res = -s where h > 0) or, SQUARED, max(0, h)^2 (res = -2 s h).
+// The inequality is strict, as in Spark's HingeAggregator: a row exactly on the kink contributes
+// nothing. Plain fp64, no transcendental.
+template <bool SQUARED>
+__device__ __forceinline__ void svc_terms(double z, double y, double& res, double& loss) {
+  const double s = 2.0 * y - 1.0;
+  const double h = 1.0 - s * z;
+  const bool active = h > 0.0;
+  if (SQUARED) {
+    res = active ? -2.0 * s * h : 0.0;
+    loss = active ? h * h : 0.0;
+  } else {
+    res = active ? -s : 0.0;
+    loss = active ? h : 0.0;
+  }
+}
+
+// Loss policy of the binary loss/gradient kernels: a compile-time choice of the per-row terms.
+constexpr int GLM_LOGISTIC = 0, GLM_HINGE = 1, GLM_SQ_HINGE = 2;
+
+template <int LOSS>
+__device__ __forceinline__ void binary_terms(double z, double y, double& res, double& loss) {
+  if constexpr (LOSS == GLM_LOGISTIC) logistic_terms(z, y, res, loss);
+  else svc_terms<LOSS == GLM_SQ_HINGE>(z, y, res, loss);
+}
+
+template <int LOSS, typename T>
+__device__ __forceinline__ void binary_terms_as(double z, double y, double& res, double& loss) {
+  if constexpr (LOSS == GLM_LOGISTIC) logistic_terms_as<T>(z, y, res, loss);
+  else svc_terms<LOSS == GLM_SQ_HINGE>(z, y, res, loss);
+}
+
 static inline int srml_status() { return (int)hipGetLastError(); }
 
 // An AMD dispatch packet carries the grid size in WORK-ITEMS as a 32-bit field: blocks * threads

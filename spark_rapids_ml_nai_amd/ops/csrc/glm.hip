@@ -428,7 +428,7 @@ __device__ __forceinline__ float softplus_f(float z) {
 }
 
 
-template <int V, bool REREAD>
+template <int V, bool REREAD, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restrict__ X, long m, int n, long ld,
                                                             const float* __restrict__ y, const double* __restrict__ w,
                                                             double b_in, const double* __restrict__ bptr,
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restr
     const double z = dot + b;
     const double yr = (double)y[r];
     double res, lt;
-    logistic_terms(z, yr, res, lt);
+    binary_terms<LOSS>(z, yr, res, lt);
     if (lane == 0) {
       loss += lt;
       gb += res;
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restr
 // Column-split variant for 1024 < n <= 4096: each of the 4 waves owns a 256*V-column slice of
 // every row (x and its gradient slice stay in registers), the block processes R rows per step;
 // per-row partial margins are exchanged through LDS (double-buffered, one barrier per step).
-template <int V, int R>
+template <int V, int R, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256, 2) void logreg_binary_split_kernel(const float* __restrict__ X, long m, int n,
                                                                      long ld, const float* __restrict__ y,
                                                                      const double* __restrict__ w, double b_in,
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void logreg_binary_split_kernel(const float
       const double z = part[buf][i][0] + part[buf][i][1] + part[buf][i][2] + part[buf][i][3] + b;
       const double yr = (double)y[r];
       double res, lt;
-      logistic_terms(z, yr, res, lt);
+      binary_terms<LOSS>(z, yr, res, lt);
       if (wid == 0 && lane == 0) {
         loss += lt;
         gb += res;
@@ -674,7 +674,7 @@ __device__ __forceinline__ void lr_margin_only(long m, int n, const float* __res
   }
 }
 
-template <int V, int R, int D, bool NT = false>
+template <int V, int R, int D, bool NT = false, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* __restrict__ X, long m, int n, long ld,
                                                                   const float* __restrict__ y,
                                                                   const double* __restrict__ w, double b_in,
@@ -689,13 +689,13 @@ __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* _
   __shared__ double part[2][R][4];
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
-  const int zmode = zfl ? zfl[LR_F_ZMODE] : 0;
-  const int zsel = zfl ? zfl[LR_F_ZSEL] : 0;
+  const int zmode = (LOSS == GLM_LOGISTIC && zfl) ? zfl[LR_F_ZMODE] : 0;  // the margin cache is logistic-only
+  const int zsel = (LOSS == GLM_LOGISTIC && zfl) ? zfl[LR_F_ZSEL] : 0;
   if (zmode == 1) {
     lr_margin_only(m, n, y, out, ws, zb, zsc, zsel, (long)blockIdx.x * rows_per_block, rows_per_block);
     return;
   }
-  double* zw = zfl ? zb + (long)(1 - zsel) * m : nullptr;
+  double* zw = (LOSS == GLM_LOGISTIC && zfl) ? zb + (long)(1 - zsel) * m : nullptr;
   const int cbase = wid * 256 * V;
   double wreg[V][4];
   int coff[V];
@@ -745,7 +745,7 @@ __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* _
       if (r < r1) {
         const double z = part[buf][i][0] + part[buf][i][1] + part[buf][i][2] + part[buf][i][3] + b;
         double res, lt;
-        logistic_terms(z, (double)y[r], res, lt);
+        binary_terms<LOSS>(z, (double)y[r], res, lt);
         if (wid == 0 && lane == 0) {
           loss += lt;
           gb += res;
@@ -815,8 +815,8 @@ __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* _
 // a wave works on 4 rows at once, the row dot product is a 16-lane DPP reduction (the DPP row
 // size) and D row batches are loaded ahead into a register ring, so each wave keeps up to
 // 4 (D + 1) rows of X in flight.
-template <int G, int D>
-__global__ __launch_bounds__(256) void logreg_binary_narrow_kernel(const float* __restrict__ X, long m, int n, long ld,
+template <int G, int D, int LOSS = GLM_LOGISTIC, int WPE = 1>
+__global__ __launch_bounds__(256, WPE) void logreg_binary_narrow_kernel(const float* __restrict__ X, long m, int n, long ld,
                                                                    const float* __restrict__ y,
                                                                    const double* __restrict__ w, double b_in,
                                                                    const double* __restrict__ bptr,
@@ -826,13 +826,13 @@ __global__ __launch_bounds__(256) void logreg_binary_narrow_kernel(const float* 
                                                                    double* __restrict__ zb,
                                                                    const double* __restrict__ zsc) {
   if (flag && *flag) return;
-  const int zmode = zfl ? zfl[LR_F_ZMODE] : 0;
-  const int zsel = zfl ? zfl[LR_F_ZSEL] : 0;
+  const int zmode = (LOSS == GLM_LOGISTIC && zfl) ? zfl[LR_F_ZMODE] : 0;  // the margin cache is logistic-only
+  const int zsel = (LOSS == GLM_LOGISTIC && zfl) ? zfl[LR_F_ZSEL] : 0;
   if (zmode == 1) {  // line-search margin cache: see logreg_binary_pf_kernel
     lr_margin_only(m, n, y, out, nullptr, zb, zsc, zsel, (long)blockIdx.x * rows_per_block, rows_per_block);
     return;
   }
-  double* zw = zfl ? zb + (long)(1 - zsel) * m : nullptr;
+  double* zw = (LOSS == GLM_LOGISTIC && zfl) ? zb + (long)(1 - zsel) * m : nullptr;
   __shared__ float gsum[4][64 * G];
   __shared__ double red[2][4];
   const double b = bptr ? *bptr : b_in;
@@ -876,7 +876,7 @@ __global__ __launch_bounds__(256) void logreg_binary_narrow_kernel(const float* 
     dot += dpp_d<0x140>(dot);  // row_mirror: every lane of the 16-lane row holds the row's dot
     if (r < r1) {
       double res, lt;
-      logistic_terms(dot + b, (double)y[r], res, lt);
+      binary_terms<LOSS>(dot + b, (double)y[r], res, lt);
       if (sub == 0) {
         loss += lt;
         gb += res;
@@ -1037,6 +1037,8 @@ SRML_API long srml_logreg_fold_ws(long m, int n, long ld, const void* X) {
 // Partial rows (= blocks) the workspace holds for m rows; row stride ((n + 3) & ~3) + 4 floats.
 SRML_API long srml_logreg_fold_parts(long m) { return m <= 0 ? 0 : logreg_grid(m); }
 
+// LOSS: the per-row terms (common.h binary_terms); every kernel choice below is the same for all losses.
+template <int LOSS = GLM_LOGISTIC>
 static int logreg_binary_launch(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                 const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
                                 hipStream_t stream, const int* zfl = nullptr, double* zb = nullptr,
@@ -1045,7 +1047,7 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
 // b: intercept by value, or (bptr != null) read on the device; flag (optional): skip when *flag != 0
 SRML_API int srml_logreg_binary2_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                      const double* bptr, const int* flag, double* out, hipStream_t stream) {
-  return logreg_binary_launch(X, m, n, ld, y, w, b, bptr, flag, out, nullptr, 0, stream);
+  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, nullptr, 0, stream);
 }
 
 // Same with the caller's partial-row workspace (srml_logreg_fold_ws floats, owned by ONE fit: the
@@ -1055,7 +1057,7 @@ SRML_API int srml_logreg_binary2_f32(const float* X, long m, int n, long ld, con
 SRML_API int srml_logreg_binary3_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                      const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
                                      hipStream_t stream) {
-  return logreg_binary_launch(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
+  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
 }
 
 // Same with the optimiser's line-search margin cache (see logreg_binary_pf_kernel): zfl = the QN
@@ -1076,13 +1078,15 @@ SRML_API int srml_logreg_binary4_f32(const float* X, long m, int n, long ld, con
                                      const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
                                      const int* zfl, double* zb, const double* zsc, hipStream_t stream) {
   if (m > 0 && !srml_logreg_zcache_ok(m, n, ld, X)) return -2;
-  return logreg_binary_launch(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream, zfl, zb, zsc);
+  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream, zfl, zb, zsc);
 }
 
+template <int LOSS>
 static int logreg_binary_launch(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                 const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
                                 hipStream_t stream, const int* zfl, double* zb, const double* zsc) {
   if (m <= 0) return 0;
+  if (LOSS != GLM_LOGISTIC && zfl) return -2;  // the line-search margin cache is logistic-only
   if (zfl && !logreg_pf_eligible(n, ld, X) && !logreg_narrow_eligible(n, ld, X)) return -2;
   if (logreg_narrow_eligible(n, ld, X)) {
     long nb = m / 256;  // ~256 rows (16 steps of 16) per block, 512 .. 4096 blocks
@@ -1093,8 +1097,19 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
     const long blocks = (m + rpb - 1) / rpb;
     const int G = (n + 63) / 64;
 #define SRML_LR_NARROW(GG, DD)                                                                                       \
-  hipLaunchKernelGGL((logreg_binary_narrow_kernel<GG, DD>), dim3((unsigned)blocks), dim3(256), 0, stream, X, m, n, ld, \
+  hipLaunchKernelGGL((logreg_binary_narrow_kernel<GG, DD, LOSS>), dim3((unsigned)blocks), dim3(256), 0, stream, X, m, n, ld, \
                      y, w, b, bptr, flag, out, rpb, zfl, zb, zsc)
+    if constexpr (LOSS != GLM_LOGISTIC) {
+      // 128 < n <= 256: the support-vector terms leave room for 4 waves per SIMD (110 VGPRs) once the
+      // ring holds one batch ahead instead of three; measured at 20M x 256: hinge 3.154 ms against 3.286 ms
+      // in the logistic shape (D = 3, 142 VGPRs, 3 waves), the logistic evaluation 3.165 ms. Timed at
+      // n = 256 only: that the rest of the range gains as well is supposed, not measured
+      if (G > 2 && G <= 4) {
+        hipLaunchKernelGGL((logreg_binary_narrow_kernel<4, 1, LOSS, 4>), dim3((unsigned)blocks), dim3(256), 0, stream,
+                           X, m, n, ld, y, w, b, bptr, flag, out, rpb, zfl, zb, zsc);
+        return srml_status();
+      }
+    }
     if (G <= 1) SRML_LR_NARROW(1, 3);
     else if (G <= 2) SRML_LR_NARROW(2, 3);
     else if (G <= 4) SRML_LR_NARROW(4, 3);
@@ -1122,7 +1137,7 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
     const long wst = ((n + 3) & ~3) + 4;
     float* fws = logreg_fold_enabled() ? fold_ws : nullptr;
 #define SRML_LR_PF(VV, RR, DD)                                                                              \
-    hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, RR, DD>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
+    hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, RR, DD, false, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
                        flag, out, rpb, fws, zfl, zb, zsc)
 #define SRML_LR_PF_V(RR, DD) \
     do { if (VS == 2) SRML_LR_PF(2, RR, DD); else if (VS == 3) SRML_LR_PF(3, RR, DD); else SRML_LR_PF(4, RR, DD); } while (0)
@@ -1131,7 +1146,7 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
     else if (dsel == 1) SRML_LR_PF_V(1, 1);
     else if (dsel == 3 && nt) {
 #define SRML_LR_PF_NT(VV)                                                                                        \
-  hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, 1, 3, true>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
+  hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, 1, 3, true, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
                      flag, out, rpb, fws, zfl, zb, zsc)
       if (VS == 2) SRML_LR_PF_NT(2);
       else if (VS == 3) SRML_LR_PF_NT(3);
@@ -1148,8 +1163,9 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
   if (split == 1 && n > 1024 && n <= 4096) {
     static const int rsel = getenv("SRML_LOGREG_R") ? atoi(getenv("SRML_LOGREG_R")) : 4;
     const int VS = (n + 1023) / 1024;
-#define SRML_LR_SPLIT(VV, RR) \
-    hipLaunchKernelGGL((logreg_binary_split_kernel<VV, RR>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, flag, out, rpb)
+#define SRML_LR_SPLIT(VV, RR)                                                                                      \
+    hipLaunchKernelGGL((logreg_binary_split_kernel<VV, RR, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
+                       flag, out, rpb)
     if (rsel == 8) {
       if (VS == 1) SRML_LR_SPLIT(1, 8); else if (VS == 2) SRML_LR_SPLIT(2, 8);
       else if (VS == 3) SRML_LR_SPLIT(3, 8); else SRML_LR_SPLIT(4, 8);
@@ -1166,9 +1182,11 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
 #define SRML_LR_LAUNCH(VV)                                                                                       \
   do {                                                                                                           \
     if (reread)                                                                                                  \
-      hipLaunchKernelGGL((logreg_binary_kernel<VV, true>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, flag, out, rpb);  \
+      hipLaunchKernelGGL((logreg_binary_kernel<VV, true, LOSS>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, \
+                         flag, out, rpb);                                                                        \
     else                                                                                                         \
-      hipLaunchKernelGGL((logreg_binary_kernel<VV, false>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, flag, out, rpb); \
+      hipLaunchKernelGGL((logreg_binary_kernel<VV, false, LOSS>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, \
+                         flag, out, rpb);                                                                        \
   } while (0)
   if (V <= 1) SRML_LR_LAUNCH(1);
   else if (V <= 2) SRML_LR_LAUNCH(2);
@@ -1183,4 +1201,14 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
 SRML_API int srml_logreg_binary_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                     double* out, hipStream_t stream) {
   return srml_logreg_binary2_f32(X, m, n, ld, y, w, b, nullptr, nullptr, out, stream);
+}
+
+// LinearSVC data term: the same kernels and internal dispatch as srml_logreg_binary3_f32 with the
+// hinge (loss 0) or squared-hinge (loss 1) per-row terms; out = [grad w (n) | grad b | loss sum].
+SRML_API int srml_svc_loss_grad_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
+                                    const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
+                                    int loss, hipStream_t stream) {
+  if (loss == 0) return logreg_binary_launch<GLM_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
+  if (loss == 1) return logreg_binary_launch<GLM_SQ_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
+  return -2;
 }

@@ -514,7 +514,7 @@ SRML_API int srml_logit_residual_wide_f64(const double* Z, long m, int K, long l
 }
 
 // ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256) void logreg_binary_lds_kernel(const T* __restrict__ X, long m, int n, long ld,
                                                                 const float* __restrict__ y,
                                                                 const double* __restrict__ w, double b_in,
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(256) void logreg_binary_lds_kernel(const T* __restr
     for (int c = lane; c < n; c += 64) dot = fma((double)row[c], w[c], dot);
     dot = wave_sum(dot);
     double res, lt;
-    logistic_terms_as<T>(dot + b, (double)y[r], res, lt);
+    binary_terms_as<LOSS, T>(dot + b, (double)y[r], res, lt);
     if (lane == 0) {
       gb += res;
       loss += lt;
@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void logreg_binary_lds_kernel(const T* __restr
   }
 }
 
-template <typename T>
+template <typename T, int LOSS = GLM_LOGISTIC>
 static int binary_lds_launch(const T* X, long m, int n, long ld, const float* y, const double* w, double b,
                              const double* bptr, const int* flag, double* out, hipStream_t stream) {
   if (m <= 0) return 0;
@@ -564,9 +564,9 @@ static int binary_lds_launch(const T* X, long m, int n, long ld, const float* y,
   blocks = (m + rpb - 1) / rpb;
   const size_t lds = (size_t)n * sizeof(double);
   if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)logreg_binary_lds_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)logreg_binary_lds_kernel<T, LOSS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
-  hipLaunchKernelGGL((logreg_binary_lds_kernel<T>), dim3((unsigned)blocks), dim3(256), lds, stream, X, m, n, ld, y, w, b,
+  hipLaunchKernelGGL((logreg_binary_lds_kernel<T, LOSS>), dim3((unsigned)blocks), dim3(256), lds, stream, X, m, n, ld, y, w, b,
                      bptr, flag, out, rpb);
   return srml_status();
 }
@@ -581,4 +581,109 @@ SRML_API int srml_logreg_binary_lds_f64(const double* X, long m, int n, long ld,
                                         double b, const double* bptr, const int* flag, double* out,
                                         hipStream_t stream) {
   return binary_lds_launch<double>(X, m, n, ld, y, w, b, bptr, flag, out, stream);
+}
+
+// LinearSVC on the LDS-accumulating kernel: loss 0 = hinge, 1 = squared hinge.
+SRML_API int srml_svc_loss_grad_lds_f32(const float* X, long m, int n, long ld, const float* y, const double* w,
+                                        double b, const double* bptr, const int* flag, double* out, int loss,
+                                        hipStream_t stream) {
+  if (loss == 0) return binary_lds_launch<float, GLM_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, stream);
+  if (loss == 1) return binary_lds_launch<float, GLM_SQ_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, stream);
+  return -2;
+}
+
+SRML_API int srml_svc_loss_grad_lds_f64(const double* X, long m, int n, long ld, const float* y, const double* w,
+                                        double b, const double* bptr, const int* flag, double* out, int loss,
+                                        hipStream_t stream) {
+  if (loss == 0) return binary_lds_launch<double, GLM_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, stream);
+  if (loss == 1) return binary_lds_launch<double, GLM_SQ_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, stream);
+  return -2;
+}
+
+// ------------------------------------------------------------------------------------------
+// Residual stage of the two-pass LinearSVC gradient: K independent models (blockIdx.y = k),
+// z = Z[r][k] + b_k; R[r][k] = hinge / squared-hinge residual (svc_terms), the bias gradient and the
+// loss block-reduced into gb[k * sgb] / loss[k * sl] (atomics), or, ws != null, stored per block in
+// the layout of the logistic stage ([gb (K) | loss (K) | -] per block) for the ordered fold.
+template <typename TZ, bool SQUARED>
+__global__ __launch_bounds__(256) void svc_residual_kernel(const TZ* __restrict__ Z, long m, int K, long ldz,
+                                                           const float* __restrict__ y, const double* __restrict__ b,
+                                                           long sb, TZ* __restrict__ R, long ldr,
+                                                           double* __restrict__ gb, long sgb,
+                                                           double* __restrict__ loss, long sl,
+                                                           const int* __restrict__ flag, double* __restrict__ ws) {
+  if (flag && *flag) return;
+  __shared__ double red[2][4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int k = blockIdx.y;
+  const double bk = b ? b[(long)k * sb] : 0.0;
+  double sg = 0.0, sls = 0.0;
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < m; r += (long)gridDim.x * 256) {
+    double res, l;
+    svc_terms<SQUARED>((double)Z[r * ldz + k] + bk, (double)y[r], res, l);
+    R[r * ldr + k] = (TZ)res;
+    sg += res;
+    sls += l;
+  }
+  sg = wave_sum(sg);
+  sls = wave_sum(sls);
+  if (lane == 0) {
+    red[0][wid] = sg;
+    red[1][wid] = sls;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  sg = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+  sls = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  if (ws) {
+    double* wb = ws + (long)blockIdx.x * (2 * K + 1);
+    wb[k] = sg;
+    wb[K + k] = sls;
+    return;
+  }
+  if (sg != 0.0) atomicAdd(&gb[(long)k * sgb], sg);
+  if (sls != 0.0) atomicAdd(&loss[(long)k * sl], sls);
+}
+
+template <typename TZ>
+static int svc_residual_launch(const TZ* Z, long m, int K, long ldz, const float* y, const double* b, long sb, int mode,
+                               TZ* R, long ldr, double* gb, long sgb, double* loss, long sl, const int* flag,
+                               double* ws, int kind, hipStream_t stream) {
+  if (m <= 0) return 0;
+  if (K < 1 || K > 16 || mode != 1 || kind < 0 || kind > 1) return -2;  // independent binary models only
+  const long blocks = logit_residual_blocks(m);
+  const dim3 grid((unsigned)blocks, (unsigned)K);
+  if (kind == 1)
+    hipLaunchKernelGGL((svc_residual_kernel<TZ, true>), grid, dim3(256), 0, stream, Z, m, K, ldz, y, b, sb, R, ldr, gb,
+                       sgb, loss, sl, flag, ws);
+  else
+    hipLaunchKernelGGL((svc_residual_kernel<TZ, false>), grid, dim3(256), 0, stream, Z, m, K, ldz, y, b, sb, R, ldr, gb,
+                       sgb, loss, sl, flag, ws);
+  int st = srml_status();
+  if (st || !ws) return st;
+  const long pst = 2L * K + 1;
+  st = srml_fold_partials_f64(ws, blocks, pst, K, K, gb, 0, sgb, flag, stream);
+  if (st) return st;
+  return srml_fold_partials_f64(ws + K, blocks, pst, K, K, loss, 0, sl, flag, stream);
+}
+
+// Arguments as srml_logit_residual_{f32,f64,det_f32} (mode must be 1: independent binary models;
+// the deterministic workspace is srml_logit_residual_ws doubles) plus kind: 0 hinge, 1 squared hinge.
+SRML_API int srml_svc_residual_f32(const float* Z, long m, int K, long ldz, const float* y, const double* b, long sb,
+                                   int mode, float* R, long ldr, double* gb, long sgb, double* loss, long sl,
+                                   const int* flag, int kind, hipStream_t stream) {
+  return svc_residual_launch(Z, m, K, ldz, y, b, sb, mode, R, ldr, gb, sgb, loss, sl, flag, nullptr, kind, stream);
+}
+
+SRML_API int srml_svc_residual_f64(const double* Z, long m, int K, long ldz, const float* y, const double* b, long sb,
+                                   int mode, double* R, long ldr, double* gb, long sgb, double* loss, long sl,
+                                   const int* flag, int kind, hipStream_t stream) {
+  return svc_residual_launch(Z, m, K, ldz, y, b, sb, mode, R, ldr, gb, sgb, loss, sl, flag, nullptr, kind, stream);
+}
+
+SRML_API int srml_svc_residual_det_f32(const float* Z, long m, int K, long ldz, const float* y, const double* b,
+                                       long sb, int mode, float* R, long ldr, double* gb, long sgb, double* loss,
+                                       long sl, const int* flag, double* ws, int kind, hipStream_t stream) {
+  if (!ws) return -2;
+  return svc_residual_launch(Z, m, K, ldz, y, b, sb, mode, R, ldr, gb, sgb, loss, sl, flag, ws, kind, stream);
 }

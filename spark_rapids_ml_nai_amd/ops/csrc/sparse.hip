@@ -46,7 +46,7 @@ __device__ __forceinline__ void block_fold2(double a, double b, bool holder, int
 }
 
 // ------------------------------------------------------------------------------------------
-template <typename T, int G>
+template <typename T, int G, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256) void csr_logreg_binary_kernel(const long* __restrict__ indptr,
                                                                 const int* __restrict__ indices,
                                                                 const T* __restrict__ data, long m,
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void csr_logreg_binary_kernel(const long* __re
     for (long p = p0 + CACHE * G + l; p < p1; p += G) dot = fma((double)data[p], w[indices[p]], dot);
     dot = group_sum<G>(dot);
     double res, lt;
-    logistic_terms_as<T>(dot + b, (double)y[r], res, lt);
+    binary_terms_as<LOSS, T>(dot + b, (double)y[r], res, lt);
     if (l == 0) {
       gb += res;
       loss += lt;
@@ -224,7 +224,7 @@ static unsigned grid_for(long rows, int G) {
   return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
-template <typename T>
+template <typename T, int LOSS = GLM_LOGISTIC>
 static int csr_logreg_launch(const long* indptr, const int* indices, const T* data, long m, long nnz, const float* y,
                              const double* w, double b, const double* bptr, const int* flag, double* grad,
                              double* tail, hipStream_t s) {
@@ -232,7 +232,7 @@ static int csr_logreg_launch(const long* indptr, const int* indices, const T* da
   const int G = pick_group(m, nnz);
   const dim3 grid(grid_for(m, G)), blk(256);
 #define SRML_CSR_LR(GG)                                                                                           \
-  hipLaunchKernelGGL((csr_logreg_binary_kernel<T, GG>), grid, blk, 0, s, indptr, indices, data, m, y, w, b, bptr, flag, \
+  hipLaunchKernelGGL((csr_logreg_binary_kernel<T, GG, LOSS>), grid, blk, 0, s, indptr, indices, data, m, y, w, b, bptr, flag, \
                      grad, tail)
   switch (G) {
     case 4: SRML_CSR_LR(4); break;
@@ -332,6 +332,25 @@ SRML_API int srml_csr_logreg_binary_f64(const long* indptr, const int* indices, 
                                         long nnz, const float* y, const double* w, double b, const double* bptr,
                                         const int* flag, double* out, hipStream_t s) {
   return csr_logreg_launch<double>(indptr, indices, data, m, nnz, y, w, b, bptr, flag, out, out + n, s);
+}
+// LinearSVC on the same kernel: loss 0 = hinge, 1 = squared hinge
+SRML_API int srml_csr_svc_loss_grad_f32(const long* indptr, const int* indices, const float* data, long m, int n,
+                                        long nnz, const float* y, const double* w, double b, const double* bptr,
+                                        const int* flag, double* out, int loss, hipStream_t s) {
+  if (loss == 0)
+    return csr_logreg_launch<float, GLM_HINGE>(indptr, indices, data, m, nnz, y, w, b, bptr, flag, out, out + n, s);
+  if (loss == 1)
+    return csr_logreg_launch<float, GLM_SQ_HINGE>(indptr, indices, data, m, nnz, y, w, b, bptr, flag, out, out + n, s);
+  return -2;
+}
+SRML_API int srml_csr_svc_loss_grad_f64(const long* indptr, const int* indices, const double* data, long m, int n,
+                                        long nnz, const float* y, const double* w, double b, const double* bptr,
+                                        const int* flag, double* out, int loss, hipStream_t s) {
+  if (loss == 0)
+    return csr_logreg_launch<double, GLM_HINGE>(indptr, indices, data, m, nnz, y, w, b, bptr, flag, out, out + n, s);
+  if (loss == 1)
+    return csr_logreg_launch<double, GLM_SQ_HINGE>(indptr, indices, data, m, nnz, y, w, b, bptr, flag, out, out + n, s);
+  return -2;
 }
 SRML_API int srml_csr_spmm_f32(const long* indptr, const int* indices, const float* data, long m, long nnz,
                                const float* W, int k, const float* bias, float* Z, hipStream_t s) {

@@ -68,6 +68,15 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_logit_residual_f64": (_P, _L, _I, _L, _P, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _P),
     "srml_logit_residual_det_f32": (_P, _L, _I, _L, _P, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _P, _P),
     "srml_logit_residual_ws": (_L, _I),
+    # LinearSVC: the logistic entry points' arguments plus the loss (0 hinge, 1 squared hinge) before the stream
+    "srml_svc_loss_grad_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _P, _I, _I, _P),
+    "srml_svc_loss_grad_lds_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _I, _P),
+    "srml_svc_loss_grad_lds_f64": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _I, _P),
+    "srml_csr_svc_loss_grad_f32": (_P, _P, _P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _I, _P),
+    "srml_csr_svc_loss_grad_f64": (_P, _P, _P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _I, _P),
+    "srml_svc_residual_f32": (_P, _L, _I, _L, _P, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _I, _P),
+    "srml_svc_residual_f64": (_P, _L, _I, _L, _P, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _I, _P),
+    "srml_svc_residual_det_f32": (_P, _L, _I, _L, _P, _P, _L, _I, _P, _L, _P, _L, _P, _L, _P, _P, _I, _P),
     "srml_xtv_mfma_ws": (_L, _I, _I),
     "srml_mbin_f32": (_P, _L, _I, _L, _P, _P, _L, _I, _P, _L, _P),
     "srml_qn_step_batch": (_P, _I, _P),

@@ -96,6 +96,19 @@ def to_spark_logistic_regression_model(model: Any) -> Any:
     return _apply_common(model, SparkLogRegModel(jm))
 
 
+def to_spark_linear_svc_model(model: Any) -> Any:
+    """``LinearSVCModel(uid, coefficients, intercept)``; ``threshold`` and the columns go over as Params."""
+    spark = _require_spark()
+    from pyspark.ml.classification import LinearSVCModel as SparkLinearSVCModel  # type: ignore
+    from pyspark.ml.linalg import DenseVector  # type: ignore
+
+    sc = spark.sparkContext
+    coef = DenseVector(model.coefficients.toArray())
+    jm = sc._jvm.org.apache.spark.ml.classification.LinearSVCModel(java_uid(sc, "linearsvc"), _py2java(sc, coef),
+                                                                   float(model.intercept))
+    return _apply_common(model, SparkLinearSVCModel(jm))
+
+
 def _impurity_calc(sc: Any, impurity: str, stats: Any, count: int) -> Any:
     jvm = sc._jvm
     arr = sc._gateway.new_array(jvm.double, len(stats))

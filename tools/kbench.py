@@ -58,6 +58,28 @@ def main():
         w = torch.randn(a.n, device=dev, dtype=torch.float64) * 0.01
         t = timeit(lambda: ops.logreg_binary_loss_grad(X, y, w, 0.1))
         res["logreg"] = {"ms": t, "TB/s": gb / t}
+    if want("svc"):
+        # one evaluation of the LinearSVC data term (ops.svc_loss_grad) for both losses against the
+        # logistic one (srml_logreg_binary3_f32: the same kernel with more arithmetic per row) in the
+        # same session: the three alternate for `rounds` rounds of 10 timed calls; ms = the median
+        # round, spread = (max - min) / median over the rounds
+        y = (torch.rand(a.m, device=dev) > 0.5).float()
+        w = torch.randn(a.n, device=dev, dtype=torch.float64) * 0.01
+        b = torch.full((1,), 0.1, device=dev, dtype=torch.float64)
+        out = torch.zeros(a.n + 2, device=dev, dtype=torch.float64)
+        ws = ops.logreg_workspace(X)
+        fns = {"logreg_binary3": lambda: ops.logistic_loss_grad(X, y, w, b, 1, out, ws=ws),
+               "svc_hinge": lambda: ops.svc_loss_grad(X, y, w, b, out, loss="hinge", ws=ws),
+               "svc_squared_hinge": lambda: ops.svc_loss_grad(X, y, w, b, out, loss="squared_hinge", ws=ws)}
+        rounds = {k: [] for k in fns}
+        for _ in range(7):
+            for k, fn in fns.items():
+                rounds[k].append(timeit(fn, 10))
+        for k, ts in rounds.items():
+            ts = sorted(ts)
+            med = ts[len(ts) // 2]
+            res[k] = {"ms": med, "min_ms": ts[0], "max_ms": ts[-1], "spread": (ts[-1] - ts[0]) / med, "TB/s": gb / med}
+        res["svc_path"] = {"fused": float(ops.svc_path(X) == "fused_svc_f32")}
     if want("xw"):
         W = torch.randn(a.n, 3, device=dev)
         t = timeit(lambda: ops.xw(X, W))
