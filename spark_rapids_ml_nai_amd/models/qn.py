@@ -41,13 +41,14 @@ QN_GRAPH = os.environ.get("SRML_QN_GRAPH", "1") != "0"
 QN_GRAPH_COMM = os.environ.get("SRML_QN_GRAPH_COMM", "1") != "0"
 # the optimiser step for N <= 16384: "mb" (default) = four multi-block launches (srml_qn_step_mb;
 # a one-rank binary LogReg fit folds the evaluation's partial rows in the first: srml_qn_step_mbf);
-# "fused" = ONE launch with software grid barriers (srml_qn_step_fused, folds likewise);
 # "single" = the one-block kernel
 QN_STEP = os.environ.get("SRML_QN_STEP", "mb")
-QN_MB = QN_STEP in ("fused", "mb")
+if QN_STEP not in ("mb", "single"):
+    raise ValueError("SRML_QN_STEP must be 'mb' or 'single', not %r" % QN_STEP)
+QN_MB = QN_STEP == "mb"
 GRAPH_STATS = {"captures": 0, "replays": 0}  # observability / tests
 STATUS = {0: "running", 1: "converged (gradient)", 2: "converged (objective change)", 3: "max iterations",
-          4: "line search failed", 5: "barrier timeout"}
+          4: "line search failed"}
 F_DONE, F_STATUS, F_ITER, F_NEVAL, F_LS, F_COUNT, F_HEAD, F_STARTED, F_BRACKET, F_ZMODE, F_ZSEL, F_NCHEAP, F_ZC = \
     range(13)
 SC_F, SC_ALPHA, SC_DGINIT, SC_GAMMA, SC_GINF, SC_ALPHA1, SC_BETA = range(7)
@@ -322,14 +323,9 @@ class DeviceQN:
         self._args = a
         self._keep = ptrs
         self._mb = None
-        lib = native.lib()
-        # the one-launch step spins on software grid barriers: only when all its blocks are
-        # guaranteed co-resident (occupancy x CUs), else the multi-launch step
-        self._fused = QN_MB and QN_STEP == "fused" and bool(lib.srml_qn_fused_resident(N))
-        self.fold: Optional[tuple] = None  # (partial-row workspace, rows, stride) the fused step folds
+        self.fold: Optional[tuple] = None  # (partial-row workspace, rows, stride) the folding step reads
         if QN_MB and N <= 16384 and os.environ.get("SRML_QN_PROBE") != "1":
-            size = int(lib.srml_qn_fused_scratch() if self._fused else lib.srml_qn_mb_scratch())
-            self._mb = ops.zeros(size, **f64)  # zeroed: the fused step's barrier words start at 0
+            self._mb = ops.zeros(int(native.lib().srml_qn_mb_scratch()), **f64)
         assert ctypes.sizeof(_QnArgs) == int(native.lib().srml_qn_args_size()), "QnArgs layout mismatch"
 
     @property
@@ -343,11 +339,7 @@ class DeviceQN:
     def step(self) -> None:
         from ..ops import native
 
-        if self._mb is not None and self._fused:
-            ws, parts, wst = self.fold if self.fold is not None else (None, 0, 0)
-            native.call("srml_qn_step_fused", ctypes.addressof(self._args), self._mb.data_ptr(),
-                        ws.data_ptr() if ws is not None else None, int(parts), int(wst), native.stream(self.device))
-        elif self._mb is not None and self.fold is not None:
+        if self._mb is not None and self.fold is not None:
             ws, parts, wst = self.fold
             native.call("srml_qn_step_mbf", ctypes.addressof(self._args), self._mb.data_ptr(), ws.data_ptr(),
                         int(parts), int(wst), native.stream(self.device))
@@ -360,10 +352,9 @@ class DeviceQN:
         return self.x.cpu().numpy().copy()
 
     def zcache_supported(self) -> bool:
-        """The margin cache needs the multi-block or single-block step (the one-launch fused step
-        ignores its flags), a backtracking Armijo search and no L1 (the orthant projection is not
-        linear in the step)."""
-        return not (self._mb is not None and self._fused) and not self.P.use_l1 and not self.P.wolfe
+        """The margin cache needs a backtracking Armijo search and no L1 (the orthant projection is
+        not linear in the step)."""
+        return not self.P.use_l1 and not self.P.wolfe
 
     def enable_zcache(self, zbuf: torch.Tensor) -> tuple:
         """Switch the margin cache on (``zbuf``: 2 m fp64): returns the evaluation's (flags, buffer,
@@ -409,7 +400,7 @@ def minimize(P: QNProblem, theta0: np.ndarray, evaluate: Callable[[torch.Tensor,
 
     ``fold`` = (workspace, rows, stride) with ``evaluate_partials(w, b, flag)``: a one-rank fit
     whose evaluation can leave per-block partial rows in the workspace instead of summing into
-    ``out``; the fused device step then folds them itself (one launch less per evaluation).
+    ``out``; the device step's first launch then folds them itself (one launch less per evaluation).
 
     ``zcache`` (2 m fp64, binary LogisticRegression on the prefetching kernel): the line-search
     margin cache — ``evaluate`` / ``evaluate_partials`` then take a ``zc`` keyword (see
@@ -505,13 +496,6 @@ def minimize(P: QNProblem, theta0: np.ndarray, evaluate: Callable[[torch.Tensor,
                 break
     torch.cuda.synchronize(device)
     res = q.info()
-    if res["status"] == "barrier timeout":
-        if q._mb is not None and q._fused:  # leave the barrier words at zero, as every launch must
-            from ..ops import native
-
-            off = int(native.lib().srml_qn_fused_barrier_offset())
-            q._mb[off: off + 1].zero_()
-        raise RuntimeError("device L-BFGS step: a grid barrier timed out (blocks not co-resident)")
     res["theta"] = q.theta()
     if not res["done"]:
         res["status"] = "evaluation cap"

@@ -3746,7 +3746,7 @@ def logistic_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, K
         dgemm(R, X, ta=True, beta=1.0, out=out[: K * n].view(K, n))
     elif path == "fused_binary_f32":
         # ws: the fit's partial-row workspace (ops.logreg_workspace), None = per-block atomic flush;
-        # leave_partials: the rows stay unfolded for the fused optimiser step (srml_qn_step_fused)
+        # leave_partials: the rows stay unfolded for the optimiser step's first launch (srml_qn_step_mbf)
         if zcache is not None:
             zfl, zb, zsc = zcache
             native.call("srml_logreg_binary4_f32", X.data_ptr(), m, n, X.stride(0), y32.data_ptr(), w.data_ptr(),

@@ -1052,8 +1052,8 @@ SRML_API int srml_logreg_binary2_f32(const float* X, long m, int n, long ld, con
 
 // Same with the caller's partial-row workspace (srml_logreg_fold_ws floats, owned by ONE fit: the
 // block partials and their fold are two launches, so interleaved fits need separate workspaces).
-// leave != 0: the rows are NOT folded into `out` here — the consumer (the fused optimiser step,
-// srml_qn_step_fused) folds them itself.
+// leave != 0: the rows are NOT folded into `out` here — the consumer (the optimiser step's first
+// launch, srml_qn_step_mbf) folds them itself.
 SRML_API int srml_logreg_binary3_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                      const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
                                      hipStream_t stream) {

@@ -3,12 +3,14 @@
 // Reference: cuML's QN solver behind LogisticRegressionMG (classification.py:957-1151,
 // lbfgs_memory=10, penalty_normalized=False): it runs its L-BFGS / OWL-QN iteration on the host
 // and pays a device round trip per function evaluation. Here the whole optimiser state lives in
-// device memory and ONE single-block kernel advances it after every (all-reduced) loss+gradient
+// device memory and an on-device step advances it after every (all-reduced) loss+gradient
 // evaluation, so a fit is a stream of   [fused loss/grad pass] -> [RCCL all-reduce] -> [qn step]
 // launches with no host synchronisation; the host only polls a `done` flag every few evaluations
-// (and the evaluation kernels early-exit once it is set).
+// (and the evaluation kernels early-exit once it is set). The step has two forms built from the
+// same pieces (the first part of this file): four multi-block launches (N <= 16384, the default)
+// and one single-block kernel (larger N, the batch of independent problems, the probe).
 //
-// State machine per call (one evaluation at the trial point xt has just been summed into `out`):
+// State machine per step (one evaluation at the trial point xt has just been summed into `out`):
 //   pass 0  smooth gradient at xt in the optimiser's (standardised) coordinates, penalty terms,
 //           directional derivatives; `out` is re-zeroed for the next evaluation.
 //   line search (backtracking Armijo — cuML's default LBFGS_LS_BT_ARMIJO — with a safeguarded quadratic
@@ -27,7 +29,7 @@
 
 namespace {
 
-constexpr int QN_T = 512;      // one block, 8 waves: the passes are latency-bound (204 VGPRs, no spills)
+constexpr int QN_T = 512;      // one block, 8 waves: the passes are latency-bound (143 VGPRs, no spills)
 constexpr int QN_NW = QN_T / 64;
 constexpr int QN_MMAX = 12;    // history capacity (runtime M <= 12; the reference uses 10)
 constexpr int QN_NV = 6 + 5 * QN_MMAX;
@@ -65,41 +67,33 @@ struct QnArgs {
   long long *probe;                  // optional: wall-clock stamps of the kernel's sections (tuning)
 };
 
-// Block-wide sum of NV per-thread values; every thread receives the totals. `red` holds
-// NV * QN_NW wave partials followed by NV totals (the totals are folded by NV threads, so no thread
-// holds NV * QN_NW LDS loads in registers).
-template <int NV>
-__device__ __forceinline__ void qn_block_sum(double (&v)[NV], double* red) {
+// ------------------------------------------------------------------------------------------
+// The pieces both forms of the step are built from. Each is the step's arithmetic or its
+// decision, written once; where the operands come from (batched loads, registers loaded at kernel
+// entry) and where a result is committed (the flags at once, or a record for a later launch) stay
+// with the caller.
+// ------------------------------------------------------------------------------------------
+
+// Block-wide sums of NV per-thread values over NW waves: `red` takes the NV * NW wave partials,
+// `tot` (LDS) the NV totals, valid for every thread on return (the totals are folded by NV threads,
+// so no thread holds NV * NW LDS loads in registers).
+template <int NW, int NV>
+__device__ __forceinline__ void qn_block_sum(const double (&v)[NV], double* red, double* tot) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const double t = wave_sum(v[i]);
-    if (lane == 0) red[i * QN_NW + wid] = t;
+    if (lane == 0) red[i * NW + wid] = t;
     __builtin_amdgcn_sched_barrier(0);  // one reduction at a time: no NV-wide live DPP temporaries
   }
   __syncthreads();
   if (threadIdx.x < NV) {
     double s = 0.0;
 #pragma unroll
-    for (int w = 0; w < QN_NW; ++w) s += red[threadIdx.x * QN_NW + w];
-    red[NV * QN_NW + threadIdx.x] = s;
+    for (int w = 0; w < NW; ++w) s += red[threadIdx.x * NW + w];
+    tot[threadIdx.x] = s;
   }
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = red[NV * QN_NW + i];
-}
-
-__device__ __forceinline__ double qn_block_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = v;
-  __syncthreads();
-  double r = red[0];
-#pragma unroll
-  for (int w = 1; w < QN_NW; ++w) r = fmax(r, red[w]);
-  __syncthreads();
-  return r;
 }
 
 // OWL-QN pseudo-gradient of f + sum c_i |x_i|
@@ -110,6 +104,279 @@ __device__ __forceinline__ double pseudo_grad(double x, double g, double c) {
   if (g + c < 0.0) return g + c;
   if (g - c > 0.0) return g - c;
   return 0.0;
+}
+
+// trial point of one element: t = x + alpha d, projected onto x's orthant where c > 0 (the L1
+// coordinates; the caller passes c = 0 without L1)
+__device__ __forceinline__ double qn_trial_value(double xv, double dv, double pv, double cv, double alpha) {
+  double t = xv + alpha * dv;
+  if (cv > 0.0) {
+    const double orth = xv != 0.0 ? (xv > 0.0 ? 1.0 : -1.0) : (pv < 0.0 ? 1.0 : (pv > 0.0 ? -1.0 : 0.0));
+    if (t * orth <= 0.0) t = 0.0;
+  }
+  return t;
+}
+
+// pass 0 of one element: returns its smooth gradient (summed evaluation value `ov`, optimiser
+// coordinates) and leaves its terms of the L2 / L1 penalties, gt.d and pg.(xt - x) in `t`
+__device__ __forceinline__ double qn_p0_terms(const QnArgs& A, double ov, double isg, double l2v, double l1v,
+                                              double xv, double dv, double pv, double xo, double (&t)[4]) {
+  const double gi = ov * A.inv_m * isg + l2v * xv;
+  t[0] = l2v * xv * xv;
+  t[1] = l1v * fabs(xv);
+  t[2] = gi * dv;
+  t[3] = pv * (xv - xo);
+  return gi;
+}
+
+// pass 1 of one element: its pseudo-gradient and new pair s = xt - x, y = gt - g, and its terms of
+// s.y, y.y, s.pg, y.pg, pg.pg and |pg| in `t`
+struct QnPair {
+  double sx, yx, pgi;
+};
+
+__device__ __forceinline__ QnPair qn_p1_terms(bool started, double xv, double gv, double xo, double go, double cv,
+                                              double (&t)[6]) {
+  const double sx = started ? xv - xo : 0.0;
+  const double yx = started ? gv - go : 0.0;
+  const double pgi = pseudo_grad(xv, gv, cv);
+  t[0] = sx * yx;
+  t[1] = yx * yx;
+  t[2] = sx * pgi;
+  t[3] = yx * pgi;
+  t[4] = pgi * pgi;
+  t[5] = fabs(pgi);
+  return {sx, yx, pgi};
+}
+
+// ... and its terms of the products with one stored pair (S_j, Y_j): s.Y_j, S_j.y, y.Y_j, S_j.pg, Y_j.pg
+__device__ __forceinline__ void qn_p1_slot_terms(double sx, double yx, double pgi, double Sj, double Yj,
+                                                 double (&t)[5]) {
+  t[0] = sx * Yj;
+  t[1] = Sj * yx;
+  t[2] = yx * Yj;
+  t[3] = Sj * pgi;
+  t[4] = Yj * pgi;
+}
+
+// Line-search decision on the objective `ft` at the trial point of step `alpha` (p02 = gt.d,
+// p03 = pg.(xt - x) of pass 0; zc / zmode: the margin cache and the mode of this evaluation):
+// accept, or the factor the step length takes for the next trial
+struct QnLs {
+  bool accept;
+  double width;
+};
+
+__device__ __forceinline__ QnLs qn_ls_decide(const QnArgs& A, double ft, double f, double alpha, double dginit,
+                                             double p02, double p03, bool bracket, bool zc, int zmode) {
+  bool accept = true;
+  double width = 1.0;
+  if (zc && zmode == 2 && isfinite(ft)) {
+    // a margins-only trial passed the test at this point: this full evaluation supplies its
+    // gradient (and the exact loss), nothing is re-tested
+  } else if (!isfinite(ft)) {
+    accept = false;
+    width = 0.5;
+  } else {
+    const double dgtest = A.l1 ? p03 : alpha * dginit;
+    if (ft > f + A.c1 * dgtest) {
+      // safeguarded quadratic interpolation through phi(0), phi'(0) alpha, phi(alpha)
+      accept = false;
+      const double den = 2.0 * (ft - f - dgtest);
+      width = den > 0.0 ? -dgtest / den : 0.5;
+      width = isfinite(width) ? fmin(0.5, fmax(0.1, width)) : 0.5;
+    } else if (A.wolfe && !A.l1 && !bracket && p02 < A.c2 * dginit) {
+      accept = false;
+      width = 2.1;
+    }
+  }
+  return {accept, width};
+}
+
+// The one-thread commits of the line search.
+// the fit ends with `status`: the evaluations that may still be queued must not read X
+__device__ __forceinline__ void qn_commit_done(int* fl, int status) {
+  fl[F_STATUS] = status;
+  fl[F_DONE] = 1;
+  fl[F_SKIPX] = 1;
+}
+
+// margin cache: the mode of the next evaluation (margins-only evaluations do not read X)
+__device__ __forceinline__ void qn_commit_zmode(int* fl, int zmode) {
+  fl[F_ZMODE] = zmode;
+  fl[F_SKIPX] = zmode == 1 ? 1 : 0;
+}
+
+// a rejected trial (its `ls`-th of this search, step alpha_tried): the search has failed, or the
+// next trial runs at step `alpha`
+__device__ __forceinline__ void qn_commit_reject(const QnArgs& A, int ls, int neval, double width, double alpha_tried,
+                                                 double alpha, double ft, bool zc, int zmode, double alpha1) {
+  int* fl = A.fl;
+  fl[F_LS] = ls;
+  fl[F_NEVAL] = neval;
+  if (ls >= A.max_ls) {
+    qn_commit_done(fl, ST_LS_FAIL);
+    return;
+  }
+  if (width < 1.0) fl[F_BRACKET] = 1;
+  A.sc[SC_ALPHA] = alpha;
+  if (zc && isfinite(ft)) {
+    // the rejected full evaluation's margins (at step alpha_tried) become z1; later trials of this
+    // search are margins-only evaluations at beta = alpha / alpha1
+    const double a1 = zmode == 0 ? alpha_tried : alpha1;
+    A.sc[SC_ALPHA1] = a1;
+    A.sc[SC_BETA] = alpha / a1;
+    qn_commit_zmode(fl, 1);
+  } else if (zc) {
+    qn_commit_zmode(fl, 0);  // a non-finite loss: no trusted margins, the next trial runs in full
+  }
+}
+
+// a trial accepted on margins only: the same point is evaluated in full next
+__device__ __forceinline__ void qn_commit_margins_accept(int* fl, int neval) {
+  fl[F_NEVAL] = neval;
+  qn_commit_zmode(fl, 2);
+}
+
+// an accepted full evaluation: its margins (the other buffer) are the new accepted point's
+__device__ __forceinline__ void qn_commit_margins_point(int* fl) {
+  fl[F_ZSEL] ^= 1;
+  qn_commit_zmode(fl, 0);
+}
+
+// The history in LDS: the Gram blocks s_i.y_j / y_i.y_j (slot-indexed), S^T pg / Y^T pg, the
+// compact-form coefficients and the chronological slot list
+struct QnHist {
+  double sy[QN_MMAX * QN_MMAX], yy[QN_MMAX * QN_MMAX];
+  double p1[QN_MMAX], p2[QN_MMAX];
+  double cf_a[QN_MMAX], cf_t[QN_MMAX];
+  int sl[QN_MMAX];
+};
+
+// what an accepted step decides; the caller commits it
+struct QnUpd {
+  int status, newp, cnt, hd, iter;
+  double gamma;
+};
+
+// One thread: history bookkeeping and the convergence test of an accepted point with objective
+// `fn` and max |pg| `ginf`. `tot`: the pass-1 totals [6 | 5 x QN_MMAX]; count / head / pre_iter /
+// pre_gamma / fh_next: the pre-step state (fh_next = the objective `past` iterations back). Inserts
+// the new pair's products into H.sy / H.yy (which hold the current blocks), fills H.p1 / H.p2 / H.sl.
+__device__ __forceinline__ QnUpd qn_history_update(const QnArgs& A, QnHist& H, const double* tot, double ginf,
+                                                   double fn, bool started, int count, int head, int pre_iter,
+                                                   double pre_gamma, double fh_next) {
+  const int M = A.M;
+  int cnt = count, hd = head, status = ST_RUNNING;
+  double gamma = started ? pre_gamma : 1.0;
+  for (int j = 0; j < M; ++j) {
+    H.p1[j] = tot[6 + 3 * QN_MMAX + j];
+    H.p2[j] = tot[6 + 4 * QN_MMAX + j];
+  }
+  const double ys = tot[0], yy = tot[1];
+  const bool newp = started && yy > 0.0 && ys > 1e-10 * yy;
+  if (newp) {
+    const int h = hd;
+    for (int j = 0; j < M; ++j) {
+      if (j == h) continue;
+      H.sy[h * M + j] = tot[6 + j];
+      H.sy[j * M + h] = tot[6 + QN_MMAX + j];
+      H.yy[h * M + j] = tot[6 + 2 * QN_MMAX + j];
+      H.yy[j * M + h] = tot[6 + 2 * QN_MMAX + j];
+    }
+    H.sy[h * M + h] = ys;
+    H.yy[h * M + h] = yy;
+    H.p1[h] = tot[2];
+    H.p2[h] = tot[3];
+    hd = (h + 1) % M;
+    cnt = cnt < M ? cnt + 1 : M;
+    gamma = ys / yy;
+  }
+  const int iter = pre_iter + (started ? 1 : 0);
+  const double fmag = fmax(fabs(fn), A.tol);
+  if (ginf <= A.tol * fmag) status = ST_CONV_GRAD;
+  if (A.past > 0 && status == ST_RUNNING && started && iter >= A.past && fabs(fh_next - fn) <= A.delta * fmag)
+    status = ST_CONV_F;
+  if (status == ST_RUNNING && iter >= A.max_iter) status = ST_MAXITER;
+  for (int c = 0; c < cnt; ++c) H.sl[c] = (hd - cnt + c + 2 * M) % M;
+  return {status, newp ? 1 : 0, cnt, hd, iter, gamma};
+}
+
+// Wave 0: compact-form coefficients into H.cf_a / H.cf_t (slot-indexed, zero for unused slots),
+// lane c = chronological pair c:
+//      t = R^-1 p1 (back substitution), a = R^-T ((D + gamma YtY) t - gamma p2) (forward),
+//      R_ce = s_c.y_e (c <= e); one broadcast + one FMA per lane per step
+__device__ __forceinline__ void qn_compact_solve(QnHist& H, int M, int cnt, double gamma) {
+  const int c = threadIdx.x;
+  const bool act = c < cnt;
+  const int slc = act ? H.sl[c] : 0;
+  double Rrow[QN_MMAX], Rcol[QN_MMAX], Yrow[QN_MMAX], tv[QN_MMAX];
+#pragma unroll
+  for (int e = 0; e < QN_MMAX; ++e) {
+    const bool ok = act && e < cnt;
+    const int sle = ok ? H.sl[e] : 0;
+    Rrow[e] = ok ? H.sy[slc * M + sle] : 0.0;
+    Rcol[e] = ok ? H.sy[sle * M + slc] : 0.0;
+    Yrow[e] = ok ? H.yy[slc * M + sle] : 0.0;
+    tv[e] = 0.0;
+  }
+  const double diag = act ? H.sy[slc * M + slc] : 1.0;
+  double acc = act ? H.p1[slc] : 0.0;
+  double tmine = 0.0;
+#pragma unroll
+  for (int e = QN_MMAX - 1; e >= 0; --e) {
+    if (e < cnt) {
+      const double te = __shfl(acc / diag, e, 64);
+      tv[e] = te;
+      if (c == e) tmine = te;
+      if (c < e) acc -= Rrow[e] * te;
+    }
+  }
+  acc = diag * tmine - gamma * (act ? H.p2[slc] : 0.0);
+#pragma unroll
+  for (int e = 0; e < QN_MMAX; ++e) acc += gamma * Yrow[e] * tv[e];
+  double amine = 0.0;
+#pragma unroll
+  for (int e = 0; e < QN_MMAX; ++e) {
+    if (e < cnt) {
+      const double ae = __shfl(acc / diag, e, 64);
+      if (c == e) amine = ae;
+      if (c > e) acc -= Rcol[e] * ae;
+    }
+  }
+  if (c < QN_MMAX) {
+    H.cf_a[c] = 0.0;
+    H.cf_t[c] = 0.0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (act) {
+    H.cf_a[slc] = amine;
+    H.cf_t[slc] = gamma * tmine;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Single-block step: one block of QN_T threads walks the whole state.
+// ------------------------------------------------------------------------------------------
+
+// every thread takes the totals back into `v`; `red` holds NV * (QN_NW + 1) doubles
+template <int NV>
+__device__ __forceinline__ void qn_sum_all(double (&v)[NV], double* red) {
+  qn_block_sum<QN_NW>(v, red, red + NV * QN_NW);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = red[NV * QN_NW + i];
+}
+
+__device__ __forceinline__ double qn_max_all(double v, double* red) {
+  v = wave_max(v);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  double r = red[0];
+#pragma unroll
+  for (int w = 1; w < QN_NW; ++w) r = fmax(r, red[w]);
+  __syncthreads();
+  return r;
 }
 
 // Element loops: every thread owns i = tid + k * QN_T and handles QN_U of its elements per batch,
@@ -138,11 +405,7 @@ __device__ void qn_set_trial(const QnArgs& A, double alpha) {
     for (int u = 0; u < QN_U; ++u) {
       const long i = i0 + (long)u * QN_T;
       if (i < A.N) {
-        double t = xv[u] + alpha * dv[u];
-        if (cv[u] > 0.0) {
-          const double orth = xv[u] != 0.0 ? (xv[u] > 0.0 ? 1.0 : -1.0) : (pv[u] < 0.0 ? 1.0 : (pv[u] > 0.0 ? -1.0 : 0.0));
-          if (t * orth <= 0.0) t = 0.0;
-        }
+        const double t = qn_trial_value(xv[u], dv[u], pv[u], cv[u], alpha);
         A.xt[i] = t;
         A.wb[i] = t * sv[u];
       }
@@ -155,13 +418,9 @@ __device__ void qn_set_trial(const QnArgs& A, double alpha) {
 
 __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
   __shared__ double red[QN_NV * (QN_NW + 1)];
-  __shared__ double cf_a[QN_MMAX], cf_t[QN_MMAX];
-  __shared__ double s_sy[QN_MMAX * QN_MMAX], s_yy[QN_MMAX * QN_MMAX];
-  __shared__ double s_p1[QN_MMAX], s_p2[QN_MMAX], s_t[QN_MMAX], s_a[QN_MMAX];
-  __shared__ int s_sl[QN_MMAX];
+  __shared__ QnHist H;
+  __shared__ QnUpd s_u;
   __shared__ double s_v[QN_NV];
-  __shared__ double s_misc[4];
-  __shared__ int s_ctl[4];
   int* fl = A.fl;
   if (fl[F_DONE]) return;
   QN_PROBE(0);
@@ -208,16 +467,14 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
     for (int u = 0; u < QN_U; ++u) {
       const long i = i0 + (long)u * QN_T;
       if (i < N) {
-        const double gi = ov[u] * A.inv_m * sv[u] + l2v[u] * xv[u];
-        A.gt[i] = gi;
-        p0[0] += l2v[u] * xv[u] * xv[u];
-        p0[1] += l1v[u] * fabs(xv[u]);
-        p0[2] += gi * dv[u];
-        p0[3] += pv[u] * (xv[u] - xo[u]);
+        double t[4];
+        A.gt[i] = qn_p0_terms(A, ov[u], sv[u], l2v[u], l1v[u], xv[u], dv[u], pv[u], xo[u], t);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p0[k] += t[k];
       }
     }
   }
-  qn_block_sum<4>(p0, red);  // every read of `out` precedes this barrier
+  qn_sum_all(p0, red);  // every read of `out` precedes this barrier
   QN_PROBE(1);
   for (long i = tid; i < Kn + A.K + 1; i += QN_T) A.out[i] = 0.0;
   const double ft = lossv * A.inv_m + 0.5 * p0[0] + p0[1];
@@ -225,74 +482,22 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
   // ---- line search decision (uniform: every thread sees the same reduced values)
   if (tid == 0 && zc && zmode == 1) fl[F_NCHEAP] += 1;
   if (started) {
-    bool accept = true;
-    double width = 1.0;
-    if (zc && zmode == 2 && isfinite(ft)) {
-      // a margins-only trial passed at this point: this full evaluation supplies its gradient
-    } else if (!isfinite(ft)) {
-      accept = false;
-      width = 0.5;
-    } else {
-      const double dgtest = A.l1 ? p0[3] : alpha * dginit;
-      if (ft > f + A.c1 * dgtest) {
-        // safeguarded quadratic interpolation through phi(0), phi'(0) alpha, phi(alpha)
-        accept = false;
-        const double den = 2.0 * (ft - f - dgtest);
-        width = den > 0.0 ? -dgtest / den : 0.5;
-        width = isfinite(width) ? fmin(0.5, fmax(0.1, width)) : 0.5;
-      } else if (A.wolfe && !A.l1 && !bracket && p0[2] < A.c2 * dginit) {
-        accept = false;
-        width = 2.1;
-      }
-    }
-    if (!accept) {
+    const QnLs d = qn_ls_decide(A, ft, f, alpha, dginit, p0[2], p0[3], bracket, zc, zmode);
+    if (!d.accept) {
       const int ls = pre_ls + 1;
       __syncthreads();
-      if (ls >= A.max_ls) {
-        if (tid == 0) {
-          fl[F_LS] = ls;
-          fl[F_NEVAL] = pre_neval + 1;
-          fl[F_STATUS] = ST_LS_FAIL;
-          fl[F_DONE] = 1;
-          fl[F_SKIPX] = 1;
-        }
-        return;
-      }
       const double alpha_tried = alpha;
-      alpha *= width;
-      qn_set_trial(A, alpha);
-      if (tid == 0) {
-        fl[F_LS] = ls;
-        fl[F_NEVAL] = pre_neval + 1;
-        if (width < 1.0) fl[F_BRACKET] = 1;
-        A.sc[SC_ALPHA] = alpha;
-        if (zc && isfinite(ft)) {
-          const double a1 = zmode == 0 ? alpha_tried : alpha1;
-          A.sc[SC_ALPHA1] = a1;
-          A.sc[SC_BETA] = alpha / a1;
-          fl[F_ZMODE] = 1;
-          fl[F_SKIPX] = 1;
-        } else if (zc) {
-          fl[F_ZMODE] = 0;
-          fl[F_SKIPX] = 0;
-        }
-      }
+      alpha *= d.width;
+      if (ls < A.max_ls) qn_set_trial(A, alpha);
+      if (tid == 0) qn_commit_reject(A, ls, pre_neval + 1, d.width, alpha_tried, alpha, ft, zc, zmode, alpha1);
       return;
     }
-    if (zc && zmode == 1) {  // accepted on margins only: evaluate the same point in full next
-      if (tid == 0) {
-        fl[F_NEVAL] = pre_neval + 1;
-        fl[F_ZMODE] = 2;
-        fl[F_SKIPX] = 0;
-      }
+    if (zc && zmode == 1) {
+      if (tid == 0) qn_commit_margins_accept(fl, pre_neval + 1);
       return;
     }
   }
-  if (tid == 0 && zc) {  // this full evaluation's margins are the accepted point's
-    fl[F_ZSEL] ^= 1;
-    fl[F_ZMODE] = 0;
-    fl[F_SKIPX] = 0;
-  }
+  if (tid == 0 && zc) qn_commit_margins_point(fl);
 
   // ---- accepted: pass 1 — pseudo-gradient at xt and every dot product of the compact form
   // 1a: pseudo-gradient at xt, new pair s = xt - x, y = gt - g (kept in the free d / wb buffers for
@@ -315,29 +520,25 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
     for (int u = 0; u < QN_U; ++u) {
       const long i = i0 + (long)u * QN_T;
       if (i < N) {
-        const double sx = started ? xv[u] - xo[u] : 0.0;
-        const double yx = started ? gv[u] - go[u] : 0.0;
-        const double pgi = pseudo_grad(xv[u], gv[u], cv[u]);
-        A.pg[i] = pgi;
-        A.d[i] = sx;
-        A.wb[i] = yx;
-        ginf = fmax(ginf, fabs(pgi));
-        v5[0] += sx * yx;
-        v5[1] += yx * yx;
-        v5[2] += sx * pgi;
-        v5[3] += yx * pgi;
-        v5[4] += pgi * pgi;
+        double t[6];
+        const QnPair e = qn_p1_terms(started, xv[u], gv[u], xo[u], go[u], cv[u], t);
+        A.pg[i] = e.pgi;
+        A.d[i] = e.sx;
+        A.wb[i] = e.yx;
+        ginf = fmax(ginf, t[5]);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v5[k] += t[k];
       }
     }
   }
   // stage the history Gram blocks in LDS: the serial small solve below must not chase global loads
   for (int i = tid; i < M * M; i += QN_T) {
-    s_sy[i] = A.SY[i];
-    s_yy[i] = A.YY[i];
+    H.sy[i] = A.SY[i];
+    H.yy[i] = A.YY[i];
   }
-  qn_block_sum<6>(v5, red);
+  qn_sum_all(v5, red);
   QN_PROBE(2);
-  ginf = qn_block_max(ginf, red);
+  ginf = qn_max_all(ginf, red);
   if (tid == 0) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) s_v[j] = v5[j];
@@ -369,14 +570,13 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
       for (int u = 0; u < QN_UB; ++u)
 #pragma unroll
         for (int jj = 0; jj < QN_JB; ++jj) {
-          w[5 * jj + 0] += sv[u] * Yv[u][jj];
-          w[5 * jj + 1] += Sv[u][jj] * yv[u];
-          w[5 * jj + 2] += yv[u] * Yv[u][jj];
-          w[5 * jj + 3] += Sv[u][jj] * pv[u];
-          w[5 * jj + 4] += Yv[u][jj] * pv[u];
+          double t[5];
+          qn_p1_slot_terms(sv[u], yv[u], pv[u], Sv[u][jj], Yv[u][jj], t);
+#pragma unroll
+          for (int k = 0; k < 5; ++k) w[5 * jj + k] += t[k];
         }
     }
-    qn_block_sum<5 * QN_JB>(w, red);
+    qn_sum_all(w, red);
     if (tid == 0) {
 #pragma unroll
       for (int jj = 0; jj < QN_JB; ++jj) {
@@ -393,125 +593,36 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
   }
 
   QN_PROBE(3);
-  // ---- lane 0: history bookkeeping and convergence (LDS + prefetched scalars only)
+  // ---- lane 0: history bookkeeping and convergence (LDS + prefetched scalars only), committed at once
   if (tid == 0) {
-    int cnt = count, hd = head, status = ST_RUNNING;
-    double gamma = started ? pre_gamma : 1.0;
-    for (int j = 0; j < M; ++j) {
-      s_p1[j] = s_v[6 + 3 * QN_MMAX + j];
-      s_p2[j] = s_v[6 + 4 * QN_MMAX + j];
-    }
-    const double ys = s_v[0], yy = s_v[1];
-    const bool newp = started && yy > 0.0 && ys > 1e-10 * yy;
-    if (newp) {
-      const int h = hd;
-      for (int j = 0; j < M; ++j) {
-        if (j == h) continue;
-        s_sy[h * M + j] = s_v[6 + j];
-        s_sy[j * M + h] = s_v[6 + QN_MMAX + j];
-        s_yy[h * M + j] = s_v[6 + 2 * QN_MMAX + j];
-        s_yy[j * M + h] = s_v[6 + 2 * QN_MMAX + j];
-      }
-      s_sy[h * M + h] = ys;
-      s_yy[h * M + h] = yy;
-      s_p1[h] = s_v[2];
-      s_p2[h] = s_v[3];
-      hd = (h + 1) % M;
-      cnt = cnt < M ? cnt + 1 : M;
-      gamma = ys / yy;
-    }
-    const double fn = ft;
-    const int iter = pre_iter + (started ? 1 : 0);
-    const double fmag = fmax(fabs(fn), A.tol);
-    if (ginf <= A.tol * fmag) status = ST_CONV_GRAD;
-    if (A.past > 0) {
-      const double fold = started ? pre_fh_next : 0.0;
-      if (status == ST_RUNNING && started && iter >= A.past && fabs(fold - fn) <= A.delta * fmag) status = ST_CONV_F;
-      A.fh[iter % A.past] = fn;
-    }
-    if (status == ST_RUNNING && iter >= A.max_iter) status = ST_MAXITER;
-    for (int c = 0; c < cnt; ++c) s_sl[c] = (hd - cnt + c + 2 * M) % M;
-    s_ctl[0] = status;
-    s_ctl[1] = newp ? 1 : 0;
-    s_ctl[2] = cnt;
-    s_misc[0] = gamma;
-    fl[F_ITER] = iter;
-    fl[F_HEAD] = hd;
-    fl[F_COUNT] = cnt;
+    const QnUpd u = qn_history_update(A, H, s_v, ginf, ft, started, count, head, pre_iter, pre_gamma, pre_fh_next);
+    s_u = u;
+    if (A.past > 0) A.fh[u.iter % A.past] = ft;
+    fl[F_ITER] = u.iter;
+    fl[F_HEAD] = u.hd;
+    fl[F_COUNT] = u.cnt;
     fl[F_NEVAL] = pre_neval + 1;
     fl[F_LS] = 0;
     fl[F_BRACKET] = 0;
     fl[F_STARTED] = 1;
-    A.sc[SC_F] = fn;
-    A.sc[SC_GAMMA] = gamma;
+    A.sc[SC_F] = ft;
+    A.sc[SC_GAMMA] = u.gamma;
     A.sc[SC_GINF] = ginf;
   }
   __syncthreads();
-  // ---- wave 0: compact-form coefficients, lane c = chronological pair c:
-  //      t = R^-1 p1 (back substitution), a = R^-T ((D + gamma YtY) t - gamma p2) (forward),
-  //      R_ce = s_c.y_e (c <= e); one broadcast + one FMA per lane per step
-  if (tid < 64) {
-    const int cnt = s_ctl[2];
-    const double gamma = s_misc[0];
-    const int c = tid;
-    const bool act = c < cnt;
-    const int slc = act ? s_sl[c] : 0;
-    double Rrow[QN_MMAX], Rcol[QN_MMAX], Yrow[QN_MMAX], tv[QN_MMAX];
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) {
-      const bool ok = act && e < cnt;
-      const int sle = ok ? s_sl[e] : 0;
-      Rrow[e] = ok ? s_sy[slc * M + sle] : 0.0;
-      Rcol[e] = ok ? s_sy[sle * M + slc] : 0.0;
-      Yrow[e] = ok ? s_yy[slc * M + sle] : 0.0;
-      tv[e] = 0.0;
-    }
-    const double diag = act ? s_sy[slc * M + slc] : 1.0;
-    double acc = act ? s_p1[slc] : 0.0;
-    double tmine = 0.0;
-#pragma unroll
-    for (int e = QN_MMAX - 1; e >= 0; --e) {
-      if (e < cnt) {
-        const double te = __shfl(acc / diag, e, 64);
-        tv[e] = te;
-        if (c == e) tmine = te;
-        if (c < e) acc -= Rrow[e] * te;
-      }
-    }
-    acc = diag * tmine - gamma * (act ? s_p2[slc] : 0.0);
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) acc += gamma * Yrow[e] * tv[e];
-    double amine = 0.0;
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) {
-      if (e < cnt) {
-        const double ae = __shfl(acc / diag, e, 64);
-        if (c == e) amine = ae;
-        if (c > e) acc -= Rcol[e] * ae;
-      }
-    }
-    if (c < QN_MMAX) {
-      cf_a[c] = 0.0;
-      cf_t[c] = 0.0;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (act) {
-      cf_a[slc] = amine;
-      cf_t[slc] = gamma * tmine;
-    }
-  }
+  if (tid < 64) qn_compact_solve(H, M, s_u.cnt, s_u.gamma);
   __syncthreads();
-  if (s_ctl[1]) {
+  if (s_u.newp) {
     for (int i = tid; i < M * M; i += QN_T) {
-      A.SY[i] = s_sy[i];
-      A.YY[i] = s_yy[i];
+      A.SY[i] = H.sy[i];
+      A.YY[i] = H.yy[i];
     }
   }
   __syncthreads();
-  const int status = s_ctl[0];
-  const bool newp = s_ctl[1] != 0;
-  const int cnt = s_ctl[2];
-  const double gamma = s_misc[0];
+  const int status = s_u.status;
+  const bool newp = s_u.newp != 0;
+  const int cnt = s_u.cnt;
+  const double gamma = s_u.gamma;
   QN_PROBE(4);
 
   // ---- pass 2: store the pair, x <- xt, g <- gt, direction d = -H pg
@@ -551,9 +662,9 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
 #pragma unroll
         for (int q = 0; q < QN_G; ++q) {
           const bool okq = c0 + q < cnt;
-          const int j = okq ? s_sl[c0 + q] : 0;
-          ca[q] = okq ? cf_a[j] : 0.0;
-          ct[q] = okq ? cf_t[j] : 0.0;
+          const int j = okq ? H.sl[c0 + q] : 0;
+          ca[q] = okq ? H.cf_a[j] : 0.0;
+          ct[q] = okq ? H.cf_t[j] : 0.0;
 #pragma unroll
           for (int u = 0; u < QN_U; ++u) {
             const long i = i0 + (long)u * QN_T;
@@ -581,15 +692,11 @@ __device__ __forceinline__ void qn_step_body(const QnArgs& A) {
     }
   }
   if (status != ST_RUNNING) {
-    if (tid == 0) {
-      fl[F_STATUS] = status;
-      fl[F_DONE] = 1;
-      fl[F_SKIPX] = 1;
-    }
+    if (tid == 0) qn_commit_done(fl, status);
     return;
   }
   QN_PROBE(5);
-  qn_block_sum<2>(p2v, red);
+  qn_sum_all(p2v, red);
   double dg = p2v[0], dd = p2v[1];
   int cnt2 = cnt;
   if (!(dg < 0.0)) {  // not a descent direction: drop the history, steepest descent
@@ -659,7 +766,8 @@ namespace {
 constexpr int MB_T = 256;
 constexpr int MB_NW = MB_T / 64;
 constexpr int MB_GMAX = 64;
-constexpr int MB_GAMAX = 512;  // K1 partial rows: the folding K1 runs ceil(N / 32) blocks
+constexpr int MBF_E = 32;      // elements per block of the folding K1 (qn_mb1f_kernel)
+constexpr int MB_GAMAX = 512;  // K1 partial rows: the folding K1 runs ceil(N / MBF_E) blocks
 constexpr int MB_PW = 6 + 5 * QN_MMAX + 1;  // pass-1 partials: 6 dots, 5 history products per slot, max |pg|
 enum {
   S_STARTED = 0, S_ITER, S_COUNT, S_HEAD, S_LS, S_NEVAL, S_BRACKET, S_F, S_ALPHA, S_DGINIT, S_GAMMA, S_FHN, S_LOSS,
@@ -673,26 +781,6 @@ enum {
   S_PC = S_PB + MB_PW * MB_GMAX,          // K3 partials [G][2]
   S_END = S_PC + 2 * MB_GMAX
 };
-
-// block-wide sums of NV values (256 threads): thread j < NV gets total j in `out` (LDS)
-template <int NV>
-__device__ __forceinline__ void mb_block_sum(const double (&v)[NV], double* red, double* out) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const double t = wave_sum(v[i]);
-    if (lane == 0) red[i * MB_NW + wid] = t;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < MB_NW; ++w) s += red[threadIdx.x * MB_NW + w];
-    out[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
 
 // grid totals of a [G][width] partial table (width <= MB_T) into LDS `tot` (all threads). Every
 // thread of the block loads: slice s = tid / width of the blocks, eight independent loads in flight
@@ -803,13 +891,7 @@ __device__ __forceinline__ MbP0In mb_p0_load(const QnArgs& A, long i, bool own) 
 }
 
 __device__ __forceinline__ void mb_p0(const QnArgs& A, long i, bool own, const MbP0In& e, double ov, double (&p0)[4]) {
-  if (!own) return;
-  const double gi = ov * A.inv_m * e.isg + e.l2v * e.xv;
-  A.gt[i] = gi;
-  p0[0] = e.l2v * e.xv * e.xv;
-  p0[1] = e.l1v * fabs(e.xv);
-  p0[2] = gi * e.dv;
-  p0[3] = e.pgv * (e.xv - e.xo);
+  if (own) A.gt[i] = qn_p0_terms(A, ov, e.isg, e.l2v, e.l1v, e.xv, e.dv, e.pgv, e.xo, p0);
 }
 
 __global__ __launch_bounds__(MB_T) void qn_mb1_kernel(QnArgs A, double* __restrict__ scr) {
@@ -837,18 +919,14 @@ __global__ __launch_bounds__(MB_T) void qn_mb1_kernel(QnArgs A, double* __restri
   double p0[4] = {0.0, 0.0, 0.0, 0.0};
   mb_p0(A, i, own, e, ov, p0);
   if (own && i < A.Kn + A.K) A.out[i] = 0.0;  // this element's evaluation sum is consumed
-  mb_block_sum<4>(p0, red, tot);
+  qn_block_sum<MB_NW>(p0, red, tot);
   if (threadIdx.x < 4) scr[S_PA + blockIdx.x * 4 + threadIdx.x] = tot[threadIdx.x];
 }
 
-// trial point of element i: t = x + alpha d, projected onto x's orthant for L1 coordinates
+// trial point of element i and its evaluation parameter
 __device__ __forceinline__ void mb_trial(const QnArgs& A, long i, double xv, double dv, double pv, double cv,
                                          double isg, double alpha) {
-  double t = xv + alpha * dv;
-  if (A.l1 && cv > 0.0) {
-    const double orth = xv != 0.0 ? (xv > 0.0 ? 1.0 : -1.0) : (pv < 0.0 ? 1.0 : (pv > 0.0 ? -1.0 : 0.0));
-    if (t * orth <= 0.0) t = 0.0;
-  }
+  const double t = qn_trial_value(xv, dv, pv, A.l1 ? cv : 0.0, alpha);
   A.xt[i] = t;
   A.wb[i] = t * isg;
 }
@@ -895,102 +973,43 @@ __global__ __launch_bounds__(MB_T) void qn_mb2_kernel(QnArgs A, double* __restri
     for (long j = N; j < A.Kn + A.K + 1; ++j) A.out[j] = 0.0;
   if (first && zc && zmode == 1) fl[F_NCHEAP] += 1;
   if (started) {
-    bool accept = true;
-    double width = 1.0;
-    if (zc && zmode == 2 && isfinite(ft)) {
-      // a margins-only trial passed the test at this point: this full evaluation supplies its
-      // gradient (and the exact loss), nothing is re-tested
-    } else if (!isfinite(ft)) {
-      accept = false;
-      width = 0.5;
-    } else {
-      const double dgtest = A.l1 ? p0[3] : alpha * dginit;
-      if (ft > f + A.c1 * dgtest) {
-        accept = false;
-        const double den = 2.0 * (ft - f - dgtest);
-        width = den > 0.0 ? -dgtest / den : 0.5;
-        width = isfinite(width) ? fmin(0.5, fmax(0.1, width)) : 0.5;
-      } else if (A.wolfe && !A.l1 && !bracket && p0[2] < A.c2 * dginit) {
-        accept = false;
-        width = 2.1;
-      }
-    }
-    if (!accept) {
+    const QnLs d = qn_ls_decide(A, ft, f, alpha, dginit, p0[2], p0[3], bracket, zc, zmode);
+    if (!d.accept) {
       const int ls = pre_ls + 1;
-      if (ls >= A.max_ls) {
-        if (first) {
-          fl[F_LS] = ls;
-          fl[F_NEVAL] = pre_neval + 1;
-          fl[F_STATUS] = ST_LS_FAIL;
-          fl[F_DONE] = 1;
-          fl[F_SKIPX] = 1;
-        }
-        return;
-      }
-      alpha *= width;
-      if (own) mb_trial(A, i, xo, dv, pv, cv, isg, alpha);
-      if (first) {
-        fl[F_LS] = ls;
-        fl[F_NEVAL] = pre_neval + 1;
-        if (width < 1.0) fl[F_BRACKET] = 1;
-        A.sc[SC_ALPHA] = alpha;
-        if (zc && isfinite(ft)) {
-          // the rejected full evaluation's margins (at step alpha0) become z1; later trials of this
-          // search are margins-only evaluations at beta = alpha / alpha1
-          const double a1 = zmode == 0 ? alpha0 : alpha1;
-          A.sc[SC_ALPHA1] = a1;
-          A.sc[SC_BETA] = alpha / a1;
-          fl[F_ZMODE] = 1;
-          fl[F_SKIPX] = 1;
-        } else if (zc) {
-          fl[F_ZMODE] = 0;  // a non-finite loss: no trusted margins, the next trial runs in full
-          fl[F_SKIPX] = 0;
-        }
-      }
+      alpha *= d.width;
+      if (ls < A.max_ls && own) mb_trial(A, i, xo, dv, pv, cv, isg, alpha);
+      if (first) qn_commit_reject(A, ls, pre_neval + 1, d.width, alpha0, alpha, ft, zc, zmode, alpha1);
       return;
     }
-    if (zc && zmode == 1) {  // accepted on margins only: evaluate the same point in full next
-      if (first) {
-        fl[F_NEVAL] = pre_neval + 1;
-        fl[F_ZMODE] = 2;
-        fl[F_SKIPX] = 0;
-      }
+    if (zc && zmode == 1) {
+      if (first) qn_commit_margins_accept(fl, pre_neval + 1);
       return;
     }
   }
   if (first) {
     scr[S_PHASE] = 1.0;
     scr[S_FT] = ft;
-    if (zc) {  // this full evaluation's margins (the other buffer) are the new accepted point's
-      fl[F_ZSEL] ^= 1;
-      fl[F_ZMODE] = 0;
-      fl[F_SKIPX] = 0;
-    }
+    if (zc) qn_commit_margins_point(fl);
   }
   // accepted: pass 1 partials of this block's elements
   double v[MB_PW];
 #pragma unroll
   for (int j = 0; j < MB_PW; ++j) v[j] = 0.0;
   if (own) {
-    const double sx = started ? xt - xo : 0.0;
-    const double yx = started ? gt - go : 0.0;
-    const double pgi = pseudo_grad(xt, gt, A.l1 ? cv : 0.0);
-    A.pg[i] = pgi;
-    A.d[i] = sx;
-    A.wb[i] = yx;
-    v[0] = sx * yx;
-    v[1] = yx * yx;
-    v[2] = sx * pgi;
-    v[3] = yx * pgi;
-    v[4] = pgi * pgi;
-    v[MB_PW - 1] = fabs(pgi);
+    double t[6];
+    const QnPair e = qn_p1_terms(started, xt, gt, xo, go, A.l1 ? cv : 0.0, t);
+    A.pg[i] = e.pgi;
+    A.d[i] = e.sx;
+    A.wb[i] = e.yx;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] = t[k];
+    v[MB_PW - 1] = t[5];
 #pragma unroll
     for (int j = 0; j < QN_MMAX; ++j) {
-      v[6 + j] = sx * Yv[j];
-      v[6 + QN_MMAX + j] = Sv[j] * yx;
-      v[6 + 2 * QN_MMAX + j] = yx * Yv[j];
-      v[6 + 3 * QN_MMAX + j] = Sv[j] * pgi;
-      v[6 + 4 * QN_MMAX + j] = Yv[j] * pgi;
+      double h[5];
+      qn_p1_slot_terms(e.sx, e.yx, e.pgi, Sv[j], Yv[j], h);
+#pragma unroll
+      for (int k = 0; k < 5; ++k) v[6 + k * QN_MMAX + j] = h[k];
     }
   }
   // block sums (the last entry is a max); history slots >= M are zero and skipped
@@ -1003,9 +1022,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb2_kernel(QnArgs A, double* __restri
     __builtin_amdgcn_sched_barrier(0);
   }
   {
-    double mx = v[MB_PW - 1];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+    const double mx = wave_max(v[MB_PW - 1]);
     if (lane == 0) red[(MB_PW - 1) * MB_NW + wid] = mx;
   }
   __syncthreads();
@@ -1020,9 +1037,8 @@ __global__ __launch_bounds__(MB_T) void qn_mb2_kernel(QnArgs A, double* __restri
 
 __global__ __launch_bounds__(MB_T) void qn_mb3_kernel(QnArgs A, double* __restrict__ scr) {
   __shared__ double tot[MB_PW], red[2 * MB_NW], t2[2];
-  __shared__ double s_sy[QN_MMAX * QN_MMAX], s_yy[QN_MMAX * QN_MMAX], s_p1[QN_MMAX], s_p2[QN_MMAX];
-  __shared__ double cf_a[QN_MMAX], cf_t[QN_MMAX], s_misc[2];
-  __shared__ int s_sl[QN_MMAX], s_ctl[4];
+  __shared__ QnHist H;
+  __shared__ QnUpd s_u;
   const int G = gridDim.x, M = A.M, tid = threadIdx.x;
   const long N = A.N;
   const long i = (long)blockIdx.x * MB_T + tid;
@@ -1051,121 +1067,35 @@ __global__ __launch_bounds__(MB_T) void qn_mb3_kernel(QnArgs A, double* __restri
   }
   if (phase != 1.0) return;
   if (tid < M * M) {
-    s_sy[tid] = sy0;
-    s_yy[tid] = yy0;
+    H.sy[tid] = sy0;
+    H.yy[tid] = yy0;
   }
-  mb_grid_sum(scr + S_PB, G, MB_PW, tot, true);  // (its barriers also publish s_sy / s_yy)
+  mb_grid_sum(scr + S_PB, G, MB_PW, tot, true);  // (its barriers also publish H.sy / H.yy)
   if (tid == 0) {
-    int cnt = pre_count, hd = head, status = ST_RUNNING;
-    double gamma = started ? pre_gamma : 1.0;
-    for (int j = 0; j < M; ++j) {
-      s_p1[j] = tot[6 + 3 * QN_MMAX + j];
-      s_p2[j] = tot[6 + 4 * QN_MMAX + j];
-    }
-    const double ys = tot[0], yy = tot[1];
-    const bool newp = started && yy > 0.0 && ys > 1e-10 * yy;
-    if (newp) {
-      const int h = hd;
-      for (int j = 0; j < M; ++j) {
-        if (j == h) continue;
-        s_sy[h * M + j] = tot[6 + j];
-        s_sy[j * M + h] = tot[6 + QN_MMAX + j];
-        s_yy[h * M + j] = tot[6 + 2 * QN_MMAX + j];
-        s_yy[j * M + h] = tot[6 + 2 * QN_MMAX + j];
-      }
-      s_sy[h * M + h] = ys;
-      s_yy[h * M + h] = yy;
-      s_p1[h] = tot[2];
-      s_p2[h] = tot[3];
-      hd = (h + 1) % M;
-      cnt = cnt < M ? cnt + 1 : M;
-      gamma = ys / yy;
-    }
     const double ginf = tot[MB_PW - 1];
-    const int iter = pre_iter + (started ? 1 : 0);
-    const double fmag = fmax(fabs(fn), A.tol);
-    if (ginf <= A.tol * fmag) status = ST_CONV_GRAD;
-    if (A.past > 0 && status == ST_RUNNING && started && iter >= A.past && fabs(fhn - fn) <= A.delta * fmag)
-      status = ST_CONV_F;
-    if (status == ST_RUNNING && iter >= A.max_iter) status = ST_MAXITER;
-    for (int c = 0; c < cnt; ++c) s_sl[c] = (hd - cnt + c + 2 * M) % M;
-    s_ctl[0] = status;
-    s_ctl[1] = newp ? 1 : 0;
-    s_ctl[2] = cnt;
-    s_ctl[3] = hd;
-    s_misc[0] = gamma;
-    s_misc[1] = ginf;
+    const QnUpd u = qn_history_update(A, H, tot, ginf, fn, started, pre_count, head, pre_iter, pre_gamma, fhn);
+    s_u = u;
     if (blockIdx.x == 0) {  // the commit record for K4
-      scr[S_STATUS] = status;
-      scr[S_NEWP] = newp ? 1.0 : 0.0;
-      scr[S_CNT] = cnt;
-      scr[S_HD] = hd;
-      scr[S_GAM] = gamma;
+      scr[S_STATUS] = u.status;
+      scr[S_NEWP] = u.newp ? 1.0 : 0.0;
+      scr[S_CNT] = u.cnt;
+      scr[S_HD] = u.hd;
+      scr[S_GAM] = u.gamma;
       scr[S_GINF] = ginf;
-      scr[S_ITERN] = iter;
+      scr[S_ITERN] = u.iter;
       scr[S_FN] = fn;
     }
   }
   __syncthreads();
-  // compact-form coefficients (wave 0, as the single-block step)
-  if (tid < 64) {
-    const int cnt = s_ctl[2];
-    const double gamma = s_misc[0];
-    const int c = tid;
-    const bool act = c < cnt;
-    const int slc = act ? s_sl[c] : 0;
-    double Rrow[QN_MMAX], Rcol[QN_MMAX], Yrow[QN_MMAX], tv[QN_MMAX];
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) {
-      const bool ok = act && e < cnt;
-      const int sle = ok ? s_sl[e] : 0;
-      Rrow[e] = ok ? s_sy[slc * M + sle] : 0.0;
-      Rcol[e] = ok ? s_sy[sle * M + slc] : 0.0;
-      Yrow[e] = ok ? s_yy[slc * M + sle] : 0.0;
-      tv[e] = 0.0;
-    }
-    const double diag = act ? s_sy[slc * M + slc] : 1.0;
-    double acc = act ? s_p1[slc] : 0.0;
-    double tmine = 0.0;
-#pragma unroll
-    for (int e = QN_MMAX - 1; e >= 0; --e) {
-      if (e < cnt) {
-        const double te = __shfl(acc / diag, e, 64);
-        tv[e] = te;
-        if (c == e) tmine = te;
-        if (c < e) acc -= Rrow[e] * te;
-      }
-    }
-    acc = diag * tmine - gamma * (act ? s_p2[slc] : 0.0);
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) acc += gamma * Yrow[e] * tv[e];
-    double amine = 0.0;
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) {
-      if (e < cnt) {
-        const double ae = __shfl(acc / diag, e, 64);
-        if (c == e) amine = ae;
-        if (c > e) acc -= Rcol[e] * ae;
-      }
-    }
-    if (c < QN_MMAX) {
-      cf_a[c] = 0.0;
-      cf_t[c] = 0.0;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (act) {
-      cf_a[slc] = amine;
-      cf_t[slc] = gamma * tmine;
-    }
-  }
+  if (tid < 64) qn_compact_solve(H, M, s_u.cnt, s_u.gamma);  // wave 0, as the single-block step
   __syncthreads();
-  const int status = s_ctl[0];
-  const bool newp = s_ctl[1] != 0;
-  const double gamma = s_misc[0];
+  const int status = s_u.status;
+  const bool newp = s_u.newp != 0;
+  const double gamma = s_u.gamma;
   if (blockIdx.x == 0 && newp)  // staged for K4 (other blocks of this launch still read A.SY / A.YY)
     for (int k = tid; k < M * M; k += MB_T) {
-      scr[S_SY + k] = s_sy[k];
-      scr[S_SY + QN_MMAX * QN_MMAX + k] = s_yy[k];
+      scr[S_SY + k] = H.sy[k];
+      scr[S_SY + QN_MMAX * QN_MMAX + k] = H.yy[k];
     }
   // pass 2: store the pair, x <- xt, g <- gt, direction (inactive slots have zero coefficients)
   double p2v[2] = {0.0, 0.0};
@@ -1182,7 +1112,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb3_kernel(QnArgs A, double* __restri
       for (int j = 0; j < QN_MMAX; ++j) {
         if (j < M) {
           const bool fresh = newp && j == head;  // the pair stored just above
-          hg += cf_a[j] * (fresh ? sv : Sv[j]) - cf_t[j] * (fresh ? yv : Yv[j]);
+          hg += H.cf_a[j] * (fresh ? sv : Sv[j]) - H.cf_t[j] * (fresh ? yv : Yv[j]);
         }
       }
       double di = -hg;
@@ -1192,7 +1122,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb3_kernel(QnArgs A, double* __restri
       p2v[1] = di * di;
     }
   }
-  mb_block_sum<2>(p2v, red, t2);
+  qn_block_sum<MB_NW>(p2v, red, t2);
   if (tid < 2) scr[S_PC + blockIdx.x * 2 + tid] = t2[tid];
 }
 
@@ -1243,11 +1173,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb4_kernel(QnArgs A, double* __restri
     }
   }
   if (status != ST_RUNNING) {
-    if (first) {
-      fl[F_STATUS] = status;
-      fl[F_DONE] = 1;
-      fl[F_SKIPX] = 1;
-    }
+    if (first) qn_commit_done(fl, status);
     return;
   }
   mb_grid_sum(scr + S_PC, G, 2, p2, false);
@@ -1291,74 +1217,20 @@ SRML_API int srml_qn_step_mb(const QnArgs* a, double* scratch, hipStream_t strea
   return srml_status();
 }
 
-// ------------------------------------------------------------------------------------------
-// Fused step: the whole optimiser step as ONE launch of G blocks (32 elements each) with three
-// software grid barriers (arrive counter + generation word in the scratch, agent-scope release /
-// acquire; G <= 512 blocks of 256 threads are co-resident on 256 CUs, and the wait is bounded by
-// wall-clock: a barrier that does not complete in ~1 s marks the step failed instead of hanging).
-// In front of pass 0 it can FOLD the binary evaluation's fp32 partial gradient rows itself
-// (`fws`: the fused binary kernel's per-block rows, single-rank fits), so an evaluation + step is
-// two launches: every kernel costs ~5 us of dispatch / ramp on its own, which the four-launch
-// step and a separate fold kernel paid six times per evaluation.
-// ------------------------------------------------------------------------------------------
-namespace {
-
-constexpr int FU_E = 32;       // elements per block
-constexpr int FU_GMAX = 512;   // N <= 16384
-constexpr int ST_BARRIER = 5;  // status: a grid barrier timed out (never expected)
-enum {
-  F_PA = S_END,                        // [G][6] pass-0 partials (+ folded loss, + folded bias grad)
-  F_PB = F_PA + 6 * FU_GMAX,           // [G][MB_PW] pass-1 partials
-  F_PC = F_PB + MB_PW * FU_GMAX,       // [G][2]
-  F_BAR = F_PC + 2 * FU_GMAX,          // 2 x u32 (arrive, generation) in one double slot
-  F_END = F_BAR + 2
-};
-
-__device__ __forceinline__ bool fu_barrier(double* scr, unsigned G) {
-  __shared__ int s_ok;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned* arrive = reinterpret_cast<unsigned*>(scr + F_BAR);
-    unsigned* gen = arrive + 1;
-    const unsigned my = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();  // release this block's partials
-    int ok = 1;
-    if (atomicAdd(arrive, 1u) == G - 1) {
-      __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(gen, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      const long long t0 = wall_clock64();
-      while (__hip_atomic_load(gen, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == my) {
-        if (wall_clock64() - t0 > 100000000LL) {  // ~1 s at the 100 MHz constant clock
-          ok = 0;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __threadfence();  // acquire the other blocks' partials
-    s_ok = ok;
-  }
-  __syncthreads();
-  return s_ok != 0;
-}
-
-}  // namespace
-
-// Fold of the binary evaluation's fp32 partial gradient rows for this block's FU_E elements
-// (columns blockIdx.x * FU_E ...): 8 lanes x float4 per row, 32 row groups, 8 rows in flight per
+// Fold of the binary evaluation's fp32 partial gradient rows for this block's MBF_E elements
+// (columns blockIdx.x * MBF_E ...): 8 lanes x float4 per row, 32 row groups, 8 rows in flight per
 // thread; the bias element and the loss are the trailing doubles of every row (summed by the
 // block owning element Kn / the last block). Returns the element's sum in `oval` and the block's
 // loss contribution in `lpart`.
-__device__ __forceinline__ void fu_fold_block(const QnArgs& A, const float* __restrict__ fws, int parts, long wst,
+__device__ __forceinline__ void mbf_fold_block(const QnArgs& A, const float* __restrict__ fws, int parts, long wst,
                                               double (*fold)[33], double* red, bool own, long i, unsigned G,
                                               double& oval, double& lpart) {
   const int tid = threadIdx.x;
   const int q = tid & 7, rg = tid >> 3;  // 8 lanes x float4 = 32 columns, 32 row groups
-  const long c = (long)blockIdx.x * FU_E + 4 * q;
+  const long c = (long)blockIdx.x * MBF_E + 4 * q;
   // the bias gradient (element Kn, owned by one block) and the loss (block G - 1): trailing
   // doubles of every row, summed over the block's 256 threads; issued first, all in flight
-  const bool has_bias = A.K == 1 && A.Kn < A.N && (long)blockIdx.x == A.Kn / FU_E;
+  const bool has_bias = A.K == 1 && A.Kn < A.N && (long)blockIdx.x == A.Kn / MBF_E;
   const bool has_loss = blockIdx.x == G - 1;
   double gb = 0.0, ls = 0.0;
   if (has_bias || has_loss)
@@ -1423,405 +1295,16 @@ __device__ __forceinline__ void fu_fold_block(const QnArgs& A, const float* __re
   __syncthreads();
 }
 
-__global__ __launch_bounds__(MB_T) void qn_fused_kernel(QnArgs A, double* __restrict__ scr,
-                                                        const float* __restrict__ fws, int parts, long wst) {
-  __shared__ double red[MB_PW * MB_NW], tot[MB_PW], fold[32][33];
-  __shared__ double s_sy[QN_MMAX * QN_MMAX], s_yy[QN_MMAX * QN_MMAX], s_p1[QN_MMAX], s_p2[QN_MMAX];
-  __shared__ double cf_a[QN_MMAX], cf_t[QN_MMAX], s_misc[2];
-  __shared__ int s_sl[QN_MMAX], s_ctl[4];
-  int* fl = A.fl;
-  if (fl[F_DONE]) return;  // uniform: no block reaches a barrier
-  const unsigned G = gridDim.x;
-  const int tid = threadIdx.x, M = A.M;
-  const long N = A.N;
-  const long i = (long)blockIdx.x * FU_E + tid;  // this thread's element (tid < FU_E)
-  const bool own = tid < FU_E && i < N;
-  const bool first = blockIdx.x == 0 && tid == 0;
-  // ---- pre-step scalars (every block reads them here; only block 0 rewrites them, after the
-  //      last barrier it takes)
-  const bool started = fl[F_STARTED] != 0;
-  const int pre_iter = fl[F_ITER], count = fl[F_COUNT], head = fl[F_HEAD], pre_ls = fl[F_LS];
-  const int pre_neval = fl[F_NEVAL];
-  const bool bracket = fl[F_BRACKET] != 0;
-  const double f = A.sc[SC_F], dginit = A.sc[SC_DGINIT], pre_gamma = A.sc[SC_GAMMA];
-  double alpha = A.sc[SC_ALPHA];
-  const double pre_fh_next = (A.past > 0 && started) ? A.fh[(pre_iter + 1) % A.past] : 0.0;
-  // ---- this block's gradient sums: folded from the evaluation's partial rows, or from `out`
-  double oval = 0.0, lpart = 0.0;
-  if (fws) {
-    fu_fold_block(A, fws, parts, wst, fold, red, own, i, G, oval, lpart);
-  } else {
-    if (own) {
-      oval = A.out[i];
-      A.out[i] = 0.0;  // consumed
-    }
-    if (first) lpart = A.out[A.Kn + A.K];  // the loss sum; zeroed by block 0 after the barrier
-  }
-  // ---- pass 0
-  double p0[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  if (own) {
-    const double xv = A.xt[i];
-    const double gi = oval * A.inv_m * (i < A.Kn ? A.isg[i % A.n] : 1.0) + A.l2[i] * xv;
-    A.gt[i] = gi;
-    p0[0] = A.l2[i] * xv * xv;
-    p0[1] = A.l1c[i] * fabs(xv);
-    p0[2] = gi * A.d[i];
-    p0[3] = A.pg[i] * (xv - A.x[i]);
-  }
-  if (tid == 0) p0[4] = lpart;
-  mb_block_sum<5>(p0, red, tot);
-  if (tid < 5) scr[F_PA + blockIdx.x * 6 + tid] = tot[tid];
-  if (!fu_barrier(scr, G)) {
-    if (first) { fl[F_STATUS] = ST_BARRIER; fl[F_DONE] = 1; }
-    return;
-  }
-  mb_grid_sum(scr + F_PA, (int)G, 6, red, false);
-  const double q0 = red[0], q1 = red[1], q2 = red[2], q3 = red[3], lossv = red[4];
-  __syncthreads();
-  const double ft = lossv * A.inv_m + 0.5 * q0 + q1;
-  if (first && !fws)  // the loss sum (read before the barrier) and bias sums without a parameter
-    for (long j = N; j < A.Kn + A.K + 1; ++j) A.out[j] = 0.0;
-  if (started) {
-    bool accept = true;
-    double width = 1.0;
-    if (!isfinite(ft)) {
-      accept = false;
-      width = 0.5;
-    } else {
-      const double dgtest = A.l1 ? q3 : alpha * dginit;
-      if (ft > f + A.c1 * dgtest) {
-        accept = false;
-        const double den = 2.0 * (ft - f - dgtest);
-        width = den > 0.0 ? -dgtest / den : 0.5;
-        width = isfinite(width) ? fmin(0.5, fmax(0.1, width)) : 0.5;
-      } else if (A.wolfe && !A.l1 && !bracket && q2 < A.c2 * dginit) {
-        accept = false;
-        width = 2.1;
-      }
-    }
-    if (!accept) {
-      const int ls = pre_ls + 1;
-      if (ls >= A.max_ls) {
-        if (first) {
-          fl[F_LS] = ls;
-          fl[F_NEVAL] = pre_neval + 1;
-          fl[F_STATUS] = ST_LS_FAIL;
-          fl[F_DONE] = 1;
-        }
-        return;
-      }
-      alpha *= width;
-      if (own) {  // next trial point
-        const double xv = A.x[i], dv = A.d[i];
-        double t = xv + alpha * dv;
-        if (A.l1 && A.l1c[i] > 0.0) {
-          const double pv = A.pg[i];
-          const double orth = xv != 0.0 ? (xv > 0.0 ? 1.0 : -1.0) : (pv < 0.0 ? 1.0 : (pv > 0.0 ? -1.0 : 0.0));
-          if (t * orth <= 0.0) t = 0.0;
-        }
-        A.xt[i] = t;
-        A.wb[i] = t * (i < A.Kn ? A.isg[i % A.n] : 1.0);
-      }
-      if (first) {
-        fl[F_LS] = ls;
-        fl[F_NEVAL] = pre_neval + 1;
-        if (width < 1.0) fl[F_BRACKET] = 1;
-        A.sc[SC_ALPHA] = alpha;
-      }
-      return;
-    }
-  }
-  // ---- accepted: pass 1 partials (own elements)
-  {
-    double v[MB_PW];
-#pragma unroll
-    for (int j = 0; j < MB_PW; ++j) v[j] = 0.0;
-    if (own) {
-      const double xv = A.xt[i], gv = A.gt[i];
-      const double sx = started ? xv - A.x[i] : 0.0;
-      const double yx = started ? gv - A.g[i] : 0.0;
-      const double pgi = pseudo_grad(xv, gv, A.l1 ? A.l1c[i] : 0.0);
-      A.pg[i] = pgi;
-      A.d[i] = sx;
-      A.wb[i] = yx;
-      v[0] = sx * yx;
-      v[1] = yx * yx;
-      v[2] = sx * pgi;
-      v[3] = yx * pgi;
-      v[4] = pgi * pgi;
-      v[MB_PW - 1] = fabs(pgi);
-#pragma unroll
-      for (int j = 0; j < QN_MMAX; ++j) {
-        if (j < M) {
-          const double Sj = A.S[(long)j * N + i], Yj = A.Y[(long)j * N + i];
-          v[6 + j] = sx * Yj;
-          v[6 + QN_MMAX + j] = Sj * yx;
-          v[6 + 2 * QN_MMAX + j] = yx * Yj;
-          v[6 + 3 * QN_MMAX + j] = Sj * pgi;
-          v[6 + 4 * QN_MMAX + j] = Yj * pgi;
-        }
-      }
-    }
-    // only wave 0 holds elements (FU_E = 32 < 64): the wave sum is the block sum
-    const int lane = tid & 63;
-    if (tid < 64) {
-#pragma unroll
-      for (int j = 0; j < MB_PW - 1; ++j) {
-        const double t = wave_sum(v[j]);
-        if (lane == 0) scr[F_PB + (long)blockIdx.x * MB_PW + j] = t;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      double mx = v[MB_PW - 1];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-      if (lane == 0) scr[F_PB + (long)blockIdx.x * MB_PW + MB_PW - 1] = mx;
-    }
-  }
-  for (int k = tid; k < M * M; k += MB_T) {  // old history blocks, before anyone commits new ones
-    s_sy[k] = A.SY[k];
-    s_yy[k] = A.YY[k];
-  }
-  if (!fu_barrier(scr, G)) {
-    if (first) { fl[F_STATUS] = ST_BARRIER; fl[F_DONE] = 1; }
-    return;
-  }
-  mb_grid_sum(scr + F_PB, G, MB_PW, tot, true);
-  if (tid == 0) {
-    int cnt = count, hd = head, status = ST_RUNNING;
-    double gamma = started ? pre_gamma : 1.0;
-    for (int j = 0; j < M; ++j) {
-      s_p1[j] = tot[6 + 3 * QN_MMAX + j];
-      s_p2[j] = tot[6 + 4 * QN_MMAX + j];
-    }
-    const double ys = tot[0], yy = tot[1];
-    const bool newp = started && yy > 0.0 && ys > 1e-10 * yy;
-    if (newp) {
-      const int h = hd;
-      for (int j = 0; j < M; ++j) {
-        if (j == h) continue;
-        s_sy[h * M + j] = tot[6 + j];
-        s_sy[j * M + h] = tot[6 + QN_MMAX + j];
-        s_yy[h * M + j] = tot[6 + 2 * QN_MMAX + j];
-        s_yy[j * M + h] = tot[6 + 2 * QN_MMAX + j];
-      }
-      s_sy[h * M + h] = ys;
-      s_yy[h * M + h] = yy;
-      s_p1[h] = tot[2];
-      s_p2[h] = tot[3];
-      hd = (h + 1) % M;
-      cnt = cnt < M ? cnt + 1 : M;
-      gamma = ys / yy;
-    }
-    const double ginf = tot[MB_PW - 1];
-    const int iter = pre_iter + (started ? 1 : 0);
-    const double fmag = fmax(fabs(ft), A.tol);
-    if (ginf <= A.tol * fmag) status = ST_CONV_GRAD;
-    if (A.past > 0 && status == ST_RUNNING && started && iter >= A.past && fabs(pre_fh_next - ft) <= A.delta * fmag)
-      status = ST_CONV_F;
-    if (status == ST_RUNNING && iter >= A.max_iter) status = ST_MAXITER;
-    for (int c = 0; c < cnt; ++c) s_sl[c] = (hd - cnt + c + 2 * M) % M;
-    s_ctl[0] = status;
-    s_ctl[1] = newp ? 1 : 0;
-    s_ctl[2] = cnt;
-    s_ctl[3] = hd;
-    s_misc[0] = gamma;
-    s_misc[1] = ginf;
-  }
-  __syncthreads();
-  if (tid < 64) {  // compact-form coefficients (wave 0)
-    const int cnt = s_ctl[2];
-    const double gamma = s_misc[0];
-    const int c = tid;
-    const bool act = c < cnt;
-    const int slc = act ? s_sl[c] : 0;
-    double Rrow[QN_MMAX], Rcol[QN_MMAX], Yrow[QN_MMAX], tv[QN_MMAX];
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) {
-      const bool ok = act && e < cnt;
-      const int sle = ok ? s_sl[e] : 0;
-      Rrow[e] = ok ? s_sy[slc * M + sle] : 0.0;
-      Rcol[e] = ok ? s_sy[sle * M + slc] : 0.0;
-      Yrow[e] = ok ? s_yy[slc * M + sle] : 0.0;
-      tv[e] = 0.0;
-    }
-    const double diag = act ? s_sy[slc * M + slc] : 1.0;
-    double acc = act ? s_p1[slc] : 0.0;
-    double tmine = 0.0;
-#pragma unroll
-    for (int e = QN_MMAX - 1; e >= 0; --e) {
-      if (e < cnt) {
-        const double te = __shfl(acc / diag, e, 64);
-        tv[e] = te;
-        if (c == e) tmine = te;
-        if (c < e) acc -= Rrow[e] * te;
-      }
-    }
-    acc = diag * tmine - gamma * (act ? s_p2[slc] : 0.0);
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) acc += gamma * Yrow[e] * tv[e];
-    double amine = 0.0;
-#pragma unroll
-    for (int e = 0; e < QN_MMAX; ++e) {
-      if (e < cnt) {
-        const double ae = __shfl(acc / diag, e, 64);
-        if (c == e) amine = ae;
-        if (c > e) acc -= Rcol[e] * ae;
-      }
-    }
-    if (c < QN_MMAX) {
-      cf_a[c] = 0.0;
-      cf_t[c] = 0.0;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (act) {
-      cf_a[slc] = amine;
-      cf_t[slc] = gamma * tmine;
-    }
-  }
-  __syncthreads();
-  const int status = s_ctl[0];
-  const bool newp = s_ctl[1] != 0;
-  const int cnt = s_ctl[2];
-  const double gamma = s_misc[0];
-  // ---- pass 2 (own elements): store the pair, x <- xt, g <- gt, direction
-  double p2v[2] = {0.0, 0.0};
-  if (own) {
-    const double xv = A.xt[i], gv = A.gt[i], sv = A.d[i], yv = A.wb[i], pv = A.pg[i];
-    if (newp) {
-      A.S[(long)head * N + i] = sv;
-      A.Y[(long)head * N + i] = yv;
-    }
-    A.x[i] = xv;
-    A.g[i] = gv;
-    if (status == ST_RUNNING) {
-      double hg = gamma * pv;
-      for (int c = 0; c < cnt; ++c) {
-        const int j = s_sl[c];
-        hg += cf_a[j] * A.S[(long)j * N + i] - cf_t[j] * A.Y[(long)j * N + i];
-      }
-      double di = -hg;
-      if (A.l1 && A.l1c[i] > 0.0 && di * pv >= 0.0) di = 0.0;
-      A.d[i] = di;
-      p2v[0] = pv * di;
-      p2v[1] = di * di;
-    }
-  }
-  if (tid < 64) {
-    const double a = wave_sum(p2v[0]), b = wave_sum(p2v[1]);
-    if (tid == 0) {
-      scr[F_PC + blockIdx.x * 2] = a;
-      scr[F_PC + blockIdx.x * 2 + 1] = b;
-    }
-  }
-  // every block is past its reads of the pre-step state and the old history blocks beyond this
-  // barrier: block 0 commits after it
-  if (!fu_barrier(scr, G)) {
-    if (first) { fl[F_STATUS] = ST_BARRIER; fl[F_DONE] = 1; }
-    return;
-  }
-  if (blockIdx.x == 0) {
-    if (newp)
-      for (int k = tid; k < M * M; k += MB_T) {
-        A.SY[k] = s_sy[k];
-        A.YY[k] = s_yy[k];
-      }
-    if (tid == 0) {
-      const int iter = pre_iter + (started ? 1 : 0);
-      if (A.past > 0) A.fh[iter % A.past] = ft;
-      fl[F_ITER] = iter;
-      fl[F_HEAD] = s_ctl[3];
-      fl[F_COUNT] = cnt;
-      fl[F_NEVAL] = pre_neval + 1;
-      fl[F_LS] = 0;
-      fl[F_BRACKET] = 0;
-      fl[F_STARTED] = 1;
-      A.sc[SC_F] = ft;
-      A.sc[SC_GAMMA] = gamma;
-      A.sc[SC_GINF] = s_misc[1];
-      if (status != ST_RUNNING) {
-        fl[F_STATUS] = status;
-        fl[F_DONE] = 1;
-      }
-    }
-  }
-  if (status != ST_RUNNING) return;
-  mb_grid_sum(scr + F_PC, (int)G, 2, red, false);
-  double dg = red[0], dd = red[1];
-  int cnt2 = cnt;
-  if (!(dg < 0.0)) {  // not a descent direction: drop the history, steepest descent (rare)
-    if (own) A.d[i] = -A.pg[i];
-    dg = -tot[4];
-    dd = tot[4];
-    cnt2 = 0;
-  }
-  const double alpha2 = cnt2 == 0 ? 1.0 / fmax(sqrt(dd), 1e-300) : 1.0;
-  if (own) {
-    const double xv = A.x[i], dv = A.d[i];
-    double t = xv + alpha2 * dv;
-    if (A.l1 && A.l1c[i] > 0.0) {
-      const double pv = A.pg[i];
-      const double orth = xv != 0.0 ? (xv > 0.0 ? 1.0 : -1.0) : (pv < 0.0 ? 1.0 : (pv > 0.0 ? -1.0 : 0.0));
-      if (t * orth <= 0.0) t = 0.0;
-    }
-    A.xt[i] = t;
-    A.wb[i] = t * (i < A.Kn ? A.isg[i % A.n] : 1.0);
-  }
-  if (first) {
-    if (cnt2 == 0) {
-      fl[F_COUNT] = 0;
-      A.sc[SC_GAMMA] = 1.0;
-    }
-    A.sc[SC_ALPHA] = alpha2;
-    A.sc[SC_DGINIT] = dg;
-  }
-}
-
-SRML_API long srml_qn_fused_scratch() { return (long)F_END; }
-
-// Offset (in doubles) of the fused step's barrier words in its scratch: a caller that abandons a
-// step whose barrier timed out zeroes them before the scratch is used again.
-SRML_API long srml_qn_fused_barrier_offset() { return (long)F_BAR; }
-
-// 1 when the fused step's G = ceil(N / 32) blocks are guaranteed co-resident on the current
-// device (occupancy x CUs >= G), so its software grid barriers cannot wait on an unscheduled
-// block; 0 otherwise (the caller takes the multi-launch step instead).
-SRML_API int srml_qn_fused_resident(long N) {
-  const long G = (N + FU_E - 1) / FU_E;
-  if (N <= 0 || G > FU_GMAX) return 0;
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(qn_fused_kernel), MB_T,
-                                                   0) != hipSuccess)
-    return 0;
-  return (long)per_cu * cus >= G ? 1 : 0;
-}
-
-// One optimiser step as ONE launch (G = ceil(N / 32) <= 512 blocks; larger N: the single-block
-// step). fws (optional): the fused binary evaluation's partial rows (parts rows of wst floats,
-// srml_logreg_binary3_f32's workspace) folded in place of `out` — single-rank fits only (a
-// multi-rank fit all-reduces `out` between the evaluation and the step). The scratch's barrier
-// words must start at zero (a zeroed allocation) and every launch leaves them so.
-SRML_API int srml_qn_step_fused(const QnArgs* a, double* scratch, const float* fws, int parts, long wst,
-                                hipStream_t stream) {
-  if (a->M < 1 || a->M > QN_MMAX || a->N <= 0 || !scratch) return (int)hipErrorInvalidValue;
-  const long G = (a->N + FU_E - 1) / FU_E;
-  if (G > FU_GMAX) return srml_qn_step(a, stream);
-  if (fws && (a->K != 1 || (wst & 3) || parts <= 0)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(qn_fused_kernel, dim3((unsigned)G), dim3(MB_T), 0, stream, *a, scratch, fws, parts, wst);
-  return srml_status();
-}
-
 // K1 of the multi-block step with the fold of the binary evaluation's partial rows in front
-// (one-rank fits): ceil(N / 32) blocks, each folds its 32 elements' columns (fu_fold_block) and
+// (one-rank fits): ceil(N / 32) blocks, each folds its 32 elements' columns (mbf_fold_block) and
 // writes the pass-0 partials; K2..K4 as in srml_qn_step_mb. Replaces fold_rows_kernel + K1.
 __global__ __launch_bounds__(MB_T) void qn_mb1f_kernel(QnArgs A, double* __restrict__ scr,
                                                        const float* __restrict__ fws, int parts, long wst) {
   __shared__ double red[4 * MB_NW], tot[4], fold[32][33];
   const bool first = blockIdx.x == 0 && threadIdx.x == 0;
   const unsigned G = gridDim.x;
-  const long i = (long)blockIdx.x * FU_E + threadIdx.x;
-  const bool own = threadIdx.x < FU_E && i < A.N;
+  const long i = (long)blockIdx.x * MBF_E + threadIdx.x;
+  const bool own = threadIdx.x < MBF_E && i < A.N;
   // every load up front (the fold's rows are read even when the fit is done: a finished fit's
   // remaining graph replays cost one wasted read each, against a round trip on every step)
   const int done = A.fl[F_DONE];
@@ -1829,7 +1312,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb1f_kernel(QnArgs A, double* __restr
   if (first) q = mb_snap_load(A);
   const MbP0In e = mb_p0_load(A, i, own);
   double oval = 0.0, lpart = 0.0;
-  fu_fold_block(A, fws, parts, wst, fold, red, own, i, G, oval, lpart);
+  mbf_fold_block(A, fws, parts, wst, fold, red, own, i, G, oval, lpart);
   if (done) {
     if (first) scr[S_PHASE] = 0.0;
     return;
@@ -1838,7 +1321,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb1f_kernel(QnArgs A, double* __restr
   if (blockIdx.x == G - 1 && threadIdx.x == 0) scr[S_LOSS] = lpart;
   double p0[4] = {0.0, 0.0, 0.0, 0.0};
   mb_p0(A, i, own, e, oval, p0);
-  mb_block_sum<4>(p0, red, tot);
+  qn_block_sum<MB_NW>(p0, red, tot);
   if (threadIdx.x < 4) scr[S_PA + blockIdx.x * 4 + threadIdx.x] = tot[threadIdx.x];
 }
 
@@ -1848,7 +1331,7 @@ SRML_API int srml_qn_step_mbf(const QnArgs* a, double* scratch, const float* fws
                               hipStream_t stream) {
   if (a->M < 1 || a->M > QN_MMAX || a->N <= 0 || !scratch || !fws) return (int)hipErrorInvalidValue;
   if (a->K != 1 || (wst & 3) || parts <= 0) return (int)hipErrorInvalidValue;
-  const long G = (a->N + MB_T - 1) / MB_T, G1 = (a->N + FU_E - 1) / FU_E;
+  const long G = (a->N + MB_T - 1) / MB_T, G1 = (a->N + MBF_E - 1) / MBF_E;
   if (G > MB_GMAX || G1 > MB_GAMAX) return (int)hipErrorInvalidValue;
   const dim3 grid((unsigned)G), blk(MB_T);
   hipLaunchKernelGGL(qn_mb1f_kernel, dim3((unsigned)G1), blk, 0, stream, *a, scratch, fws, parts, wst);

@@ -26,8 +26,7 @@ _D = ctypes.c_double
 _F = ctypes.c_float
 
 # name -> argtypes (restype: int status, except the size queries in _LONG_RESULT)
-_LONG_RESULT = ("srml_rf_bootstrap_ws", "srml_logreg_fold_ws", "srml_qn_mb_scratch", "srml_qn_fused_scratch",
-                "srml_qn_fused_barrier_offset",
+_LONG_RESULT = ("srml_rf_bootstrap_ws", "srml_logreg_fold_ws", "srml_qn_mb_scratch",
                 "srml_logreg_fold_parts", "srml_qn_args_size", "srml_logit_residual_ws", "srml_xtv_mfma_ws",
                 "srml_rf_partition_ws", "srml_dbscan_labels_ws", "srml_umap_categorical_ws",
                 "srml_umap_epoch_sync_ws",
@@ -84,14 +83,10 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_mlogit_supported": (_I, _I),
     "srml_qn_step": (_P, _P),
     "srml_qn_step_mb": (_P, _P, _P),
-    "srml_qn_step_fused": (_P, _P, _P, _I, _L, _P),
     "srml_qn_step_mbf": (_P, _P, _P, _I, _L, _P),
     "srml_kmeans_lloyd_small": (_P, _L, _I, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P),
     "srml_kmeans_lloyd_mfma": (_P, _L, _I, _L, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P),
     "srml_kmeans_small_update": (_P, _I, _I, _P, _P, _P, _D, _P, _P, _P, _P),
-    "srml_qn_fused_scratch": (),
-    "srml_qn_fused_barrier_offset": (),
-    "srml_qn_fused_resident": (_L,),
     "srml_qn_mb_scratch": (),
     "srml_kmeanspp_gram": (_P, _I, _L, _P, _I, _I, ctypes.c_ulonglong, _P, _P),
     "srml_qn_max_history": (),

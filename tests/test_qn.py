@@ -284,12 +284,12 @@ def test_qn_multiblock_step_matches_single_block(gpu_device, K, l1, n, monkeypat
         out += _ref_loss_grad(Xg, yg, w, b, K).to(gpu_device)
 
     res = {}
-    for mode in ("single", "mb", "fused"):  # srml_qn_step / srml_qn_step_mb / srml_qn_step_fused
+    for mode in ("single", "mb"):  # srml_qn_step / srml_qn_step_mb
         monkeypatch.setattr(qnm, "QN_MB", mode != "single")
         monkeypatch.setattr(qnm, "QN_STEP", mode)
         res[mode] = minimize(P, np.zeros(N), ev_gpu, None, gpu_device, batch=4)
     a = res["single"]
-    for mode in ("mb", "fused"):
+    for mode in ("mb",):
         b = res[mode]
         info = {k: (a[k], b[k]) for k in ("iter", "n_evals", "status", "f")}
         info["mode"] = mode
@@ -303,10 +303,65 @@ def test_qn_multiblock_step_matches_single_block(gpu_device, K, l1, n, monkeypat
 
 
 @pytest.mark.gpu
-def test_logistic_fit_fused_fold_matches_unfused(gpu_device, monkeypatch):
+@pytest.mark.parametrize("K,n,M", [
+    (1, 5, 10),    # N = 6: part of one wave
+    (1, 255, 10),  # N = 256: exactly one block of the multi-block step
+    (1, 256, 10),  # N = 257: a second block that owns one element
+    (3, 21, 3),    # N = 66, multinomial: the three-slot history ring wraps several times
+])
+def test_qn_step_modes_agree_at_block_edges_and_ring_wrap(gpu_device, K, n, M, monkeypatch):
+    """The single-block and the multi-block step take the same decisions where the code they share
+    meets a wave / block edge or a wrapped history ring (smooth problems: same trajectory)."""
+    from spark_rapids_ml_nai_amd.models import qn as qnm
+
+    m = 500
+    g = torch.Generator().manual_seed(31 + K)
+    Xc = torch.randn(m, n, generator=g, dtype=torch.float64)
+    if K == 1:
+        y = (Xc[:, 0] + 0.5 * torch.randn(m, generator=g, dtype=torch.float64) > 0).double()
+    else:
+        y = torch.argmax(Xc[:, :K] + 0.5 * torch.randn(m, K, generator=g, dtype=torch.float64), 1).double()
+    N = K * n + K
+    P = QNProblem(n=n, K=K, fit_intercept=True, m_total=float(m),
+                  l2=np.concatenate([np.full(K * n, 0.01), np.zeros(K)]), l1=np.zeros(N),
+                  inv_sigma=np.linspace(0.5, 1.5, n), max_iter=40, tol=1e-12, M=M)
+    Xg, yg = Xc.to(gpu_device), y.to(gpu_device)
+
+    def ev_gpu(w, b, flag, out):
+        out += _ref_loss_grad(Xg, yg, w, b, K).to(gpu_device)
+
+    res = {}
+    for mode in ("single", "mb"):  # srml_qn_step / srml_qn_step_mb
+        monkeypatch.setattr(qnm, "QN_MB", mode != "single")
+        monkeypatch.setattr(qnm, "QN_STEP", mode)
+        res[mode] = minimize(P, np.zeros(N), ev_gpu, None, gpu_device, batch=4)
+    a, b = res["single"], res["mb"]
+    info = {k: (a[k], b[k]) for k in ("iter", "n_evals", "status", "f")}
+    print(info)
+    assert M > 3 or a["iter"] >= 12, info  # the three-slot ring has wrapped several times
+    assert a["iter"] == b["iter"] and a["status"] == b["status"] and a["n_evals"] == b["n_evals"], info
+    assert abs(a["f"] - b["f"]) <= 1e-10 * abs(a["f"]), info
+    np.testing.assert_allclose(b["theta"], a["theta"], rtol=1e-6, atol=1e-8)
+
+
+def test_qn_step_option_rejects_unknown_values(monkeypatch):
+    """SRML_QN_STEP takes 'mb' or 'single'; anything else (the removed 'fused' included) is an error
+    naming the two, not a silent fall-back to the single-block step."""
+    import importlib.util
+
+    from spark_rapids_ml_nai_amd.models import qn as qnm
+
+    monkeypatch.setenv("SRML_QN_STEP", "fused")
+    spec = importlib.util.spec_from_file_location("spark_rapids_ml_nai_amd.models._qn_option_check", qnm.__file__)
+    with pytest.raises(ValueError, match="'mb' or 'single'"):
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+
+
+@pytest.mark.gpu
+def test_logistic_fit_step_fold_matches_evaluation_fold(gpu_device, monkeypatch):
     """One-rank binary LogReg with the fold moved into the optimiser step (the evaluation leaves
-    its partial rows; srml_qn_step_mbf / srml_qn_step_fused fold them) reproduces the fit whose
-    evaluation folds them itself."""
+    its partial rows; srml_qn_step_mbf folds them) reproduces the fit whose evaluation folds them
+    itself."""
     from spark_rapids_ml_nai_amd import ops
     from spark_rapids_ml_nai_amd.models import qn as qnm
     from spark_rapids_ml_nai_amd.models.logistic import logistic_fit
@@ -320,13 +375,13 @@ def test_logistic_fit_fused_fold_matches_unfused(gpu_device, monkeypatch):
     assert ops.logreg_workspace(Xt) is not None and ops.logistic_path(Xt, 1) == "fused_binary_f32"
     ctx = WorkerContext.single(gpu_device)
     out = {}
-    for mode in ("single", "mb", "fused"):  # unfolded single-block step / srml_qn_step_mbf / fused
+    for mode in ("single", "mb"):  # unfolded single-block step / srml_qn_step_mbf
         monkeypatch.setattr(qnm, "QN_MB", mode != "single")
         monkeypatch.setattr(qnm, "QN_STEP", mode)
         out[mode] = logistic_fit(Xt, yt, m, ctx, reg=1e-3, l1_ratio=0.0, fit_intercept=True,
                                  standardization=True, max_iter=60, tol=1e-10)
     a = out["single"]
-    for mode in ("mb", "fused"):
+    for mode in ("mb",):
         b = out[mode]
         # the fp32 evaluation's partials are summed in another order, so a convergence test at
         # tol 1e-10 (below fp32 noise) may stop at another iteration: compare the optimum
