@@ -7,7 +7,7 @@ done by the reference in cupy and the moments exchanged as JSON through the Spar
 
 MI355X design:
 * every objective/gradient evaluation is ONE fused pass over the resident shard: binary
-  ``srml_logreg_binary2_f32`` (margin, softplus loss, residual and X^T r from registers),
+  ``srml_logreg_binary_f32`` (margin, softplus loss, residual and X^T r from registers),
   multinomial ``srml_mlogit_f32`` (K margins, softmax, K gradient rows from one read of each row),
   CSR kernels for sparse input, an LDS-accumulating pass for fp64 / wide rows; then ONE RCCL
   all-reduce of [grad (K n), grad_b (K), loss] in fp64;

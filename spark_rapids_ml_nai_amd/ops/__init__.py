@@ -325,8 +325,9 @@ def logreg_binary_loss_grad(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, b
     wf = _c(w.to(device=X.device, dtype=torch.float64))
     yf = _c(y.to(torch.float32))
     ws = logreg_workspace(X)
-    native.call("srml_logreg_binary3_f32", X.data_ptr(), m, n, X.stride(0), yf.data_ptr(), wf.data_ptr(), float(b),
-                None, None, out.data_ptr(), ws.data_ptr() if ws is not None else None, 0, native.stream(X.device))
+    native.call("srml_logreg_binary_f32", X.data_ptr(), m, n, X.stride(0), yf.data_ptr(), wf.data_ptr(), float(b),
+                None, None, out.data_ptr(), ws.data_ptr() if ws is not None else None, 0, None, None, None,
+                native.stream(X.device))
     return out
 
 
@@ -3505,25 +3506,39 @@ def _is_csr(X) -> bool:
     return hasattr(X, "indptr") and hasattr(X, "indices")
 
 
+def _binary_path(X, tag: str, det: str) -> str:
+    """The pass of a one-model data term for X: ``logistic_path(X, 1)`` (tag "binary") and
+    ``svc_path(X)`` (tag "svc") are this tree; ``det`` names its deterministic fp32 pass."""
+    if _is_csr(X):
+        return "csr_" + tag if X.data.is_cuda else "torch-cpu"
+    if not X.is_cuda:
+        return "torch-cpu"
+    n = X.shape[1]
+    f32 = X.dtype == torch.float32
+    if deterministic() and f32:
+        return det
+    if f32 and n <= 4096:
+        return "fused_%s_f32" % tag
+    if X.dtype in (torch.float32, torch.float64) and n <= 16384:
+        return "lds_%s_%s" % (tag, "f32" if f32 else "f64")
+    return "two_pass_%s_%s" % (tag, "f32" if f32 else "f64")
+
+
 def logistic_path(X, K: int) -> str:
     """Which device pass ``logistic_loss_grad`` uses for X (reported by the fit / asserted in tests).
     Every device input runs on the srml kernels (dense fp64 multinomial: margins and X^T R on the
     fp64 MFMA GEMM around the fp64 softmax residual kernel)."""
+    if K == 1:
+        return _binary_path(X, "binary", "two_pass_deterministic_f32")
     if _is_csr(X):
         if not X.data.is_cuda:
             return "torch-cpu"
-        return "csr_binary" if K == 1 else ("csr_spmm" if K <= 16 else "csr_wide")
+        return "csr_spmm" if K <= 16 else "csr_wide"
     if not X.is_cuda:
         return "torch-cpu"
-    m, n = X.shape
+    n = X.shape[1]
     if deterministic() and X.dtype == torch.float32 and K <= 16:
         return "two_pass_deterministic_f32"
-    if K == 1:
-        if X.dtype == torch.float32 and n <= 4096:
-            return "fused_binary_f32"
-        if X.dtype in (torch.float32, torch.float64) and n <= 16384:
-            return "lds_binary_" + ("f32" if X.dtype == torch.float32 else "f64")
-        return "two_pass_binary_f32" if X.dtype == torch.float32 else "two_pass_binary_f64"
     if X.dtype == torch.float32 and K <= 16:
         fused = os.environ.get("SRML_LOGREG_FUSED", "0") == "1" and int(native.lib().srml_mlogit_supported(n, K))
         return "fused_multinomial_f32" if fused else "two_pass_multinomial_f32"
@@ -3575,12 +3590,15 @@ def mbin_supported(X, M: int) -> bool:
 
 def _glm_two_pass(X: torch.Tensor, y32: torch.Tensor, W: torch.Tensor, b: torch.Tensor, sb: int, mode: int,
                   grad: torch.Tensor, so_c: int, so_k: int, gb: torch.Tensor, sgb: int, loss: torch.Tensor, sl: int,
-                  flag: Optional[torch.Tensor], zc: Optional[tuple] = None) -> None:
+                  flag: Optional[torch.Tensor], zc: Optional[tuple] = None, family: str = "logit",
+                  kind: Tuple[int, ...] = ()) -> None:
     """Two passes over X for K margins: Z = X W^T (``srml_xw_f32``, one bandwidth-bound pass for
     K <= 32), the residual stage on the device (``srml_logit_residual_f32``: softmax (mode 0) or K
     independent sigmoids (mode 1), bias gradients and losses block-reduced into fp64), then
     grad += R^T X (``srml_xtv2_f32``, one pass for K <= 16). ``W`` (K, n) rows (any row stride),
-    output locations given by base tensors + element strides."""
+    output locations given by base tensors + element strides. ``family`` "svc" with ``kind`` =
+    (loss,): the support-vector residual kernels (``srml_svc_residual_f32``, K = 1, mode 1), which
+    take the loss before the stream."""
     m, n = X.shape
     K = W.shape[0]
     st = native.stream(X.device)
@@ -3612,15 +3630,34 @@ def _glm_two_pass(X: torch.Tensor, y32: torch.Tensor, W: torch.Tensor, b: torch.
         L = native.lib()
         ws = torch.empty(max(int(L.srml_logit_residual_ws(m, K)), int(L.srml_xtv_mfma_ws(m, n, K)), 1),
                          dtype=torch.float64, device=X.device)
-        native.call("srml_logit_residual_det_f32", Z.data_ptr(), m, K, Z.stride(0), yp, b.data_ptr(), sb, mode,
-                    R.data_ptr(), K, gb.data_ptr(), sgb, loss.data_ptr(), sl, fp, ws.data_ptr(), st)
+        native.call("srml_%s_residual_det_f32" % family, Z.data_ptr(), m, K, Z.stride(0), yp, b.data_ptr(), sb, mode,
+                    R.data_ptr(), K, gb.data_ptr(), sgb, loss.data_ptr(), sl, fp, ws.data_ptr(), *kind, st)
         native.call("srml_xtv_mfma_det_f32", X.data_ptr(), m, n, X.stride(0), R.data_ptr(), K, K, grad.data_ptr(),
                     so_c, so_k, fp, ws.data_ptr(), st)
         return
-    native.call("srml_logit_residual_f32", Z.data_ptr(), m, K, Z.stride(0), yp, b.data_ptr(), sb,
-                mode, R.data_ptr(), K, gb.data_ptr(), sgb, loss.data_ptr(), sl, fp, st)
+    native.call("srml_%s_residual_f32" % family, Z.data_ptr(), m, K, Z.stride(0), yp, b.data_ptr(), sb,
+                mode, R.data_ptr(), K, gb.data_ptr(), sgb, loss.data_ptr(), sl, fp, *kind, st)
     fn = "srml_xtv_mfma_f32" if K >= XTV_MFMA_MIN_K else "srml_xtv2_f32"
     native.call(fn, X.data_ptr(), m, n, X.stride(0), R.data_ptr(), K, K, grad.data_ptr(), so_c, so_k, fp, st)
+
+
+def _binary_two_pass(X: torch.Tensor, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor,
+                     flag: Optional[torch.Tensor], family: str = "logit", kind: Tuple[int, ...] = ()) -> None:
+    """One model (sigmoid, or the support-vector terms of ``family`` "svc") wider than the
+    LDS-resident kernels, or any fp32 width in deterministic mode. fp32: ``_glm_two_pass``; fp64:
+    margins and X^T r on the fp64 MFMA GEMM (split-K over rows), the residual / loss / bias gradient
+    in one fp64 pass (``srml_logit_residual_f64`` / ``srml_svc_residual_f64``)."""
+    m, n = X.shape
+    if X.dtype == torch.float32:
+        _glm_two_pass(X, y32, w.view(1, n), b, 1, 1, out, 1, n, out[n:], 1, out[n + 1:], 1, flag, family=family,
+                      kind=kind)
+        return
+    z = dgemm(X, w.view(n, 1))
+    r = zeros((m, 1), dtype=torch.float64, device=X.device)  # stays 0 if the done flag skips it
+    native.call("srml_%s_residual_f64" % family, z.data_ptr(), m, 1, 1, _c(y32).data_ptr(), b.data_ptr(), 1, 1,
+                r.data_ptr(), 1, out[n:].data_ptr(), 1, out[n + 1:].data_ptr(), 1,
+                flag.data_ptr() if flag is not None else None, *kind, native.stream(X.device))
+    dgemm(X, r, ta=True, beta=1.0, out=out[:n].view(n, 1))
 
 
 def logistic_loss_grad_multi(X: torch.Tensor, y32: torch.Tensor, WB: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -3662,7 +3699,7 @@ def logistic_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, K
     classes (labels 0..K-1). ``w`` (K*n) and ``b`` (K) are fp64 device tensors read by the kernel
     (no host round trip); ``flag`` (device int32, optional): the kernels skip once it is non-zero.
     ``zcache`` = (QN flags, 2 m K fp64 margin buffers, QN scalars): the optimiser's line-search
-    margin cache — binary: the narrow / prefetching kernels (``srml_logreg_binary4_f32``; the
+    margin cache — binary: the narrow / prefetching kernels (``srml_logreg_binary_f32``; the
     caller checked ``logreg_zcache_ok``); multinomial (``two_pass_multinomial_f32``): the margin /
     residual / X^T R passes. X: dense (m, n) or CSR."""
     path = logistic_path(X, K)
@@ -3719,16 +3756,8 @@ def logistic_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, K
         out[: K * n] += csr_spmtm(X, R).t().reshape(-1)
     elif path in ("csr_wide", "two_pass_wide_f32"):
         _glm_wide(X, y32, w.view(K, n), b, out, flag)
-    elif path == "two_pass_binary_f32":  # wider than the LDS-resident binary kernels
-        _glm_two_pass(X, y32, w.view(1, n), b, 1, 1, out, 1, n, out[n:], 1, out[n + 1:], 1, flag)
-    elif path == "two_pass_binary_f64":
-        # fp64 inputs wider than the LDS kernels: margins and X^T r on the fp64 MFMA GEMM (split-K
-        # over rows), the residual / loss / bias gradient in one fp64 pass (srml_logit_residual_f64)
-        z = dgemm(X, w.view(n, 1))
-        r = zeros((m, 1), dtype=torch.float64, device=dev)  # stays 0 if the done flag skips it
-        native.call("srml_logit_residual_f64", z.data_ptr(), m, 1, 1, _c(y32).data_ptr(), b.data_ptr(), 1, 1,
-                    r.data_ptr(), 1, out[n:].data_ptr(), 1, out[n + 1:].data_ptr(), 1, fp, st)
-        dgemm(X, r, ta=True, beta=1.0, out=out[:n].view(n, 1))
+    elif path in ("two_pass_binary_f32", "two_pass_binary_f64") or (path == "two_pass_deterministic_f32" and K == 1):
+        _binary_two_pass(X, y32, w, b, out, flag)
     elif path == "two_pass_multinomial_f64":
         # fp64 softmax: margins Z = X W^T and the gradient R^T X on the fp64 MFMA GEMM, the
         # residual / bias gradient / loss in one fp64 pass (srml_logit_residual_f64, mode 0; K > 16:
@@ -3747,27 +3776,19 @@ def logistic_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, K
     elif path == "fused_binary_f32":
         # ws: the fit's partial-row workspace (ops.logreg_workspace), None = per-block atomic flush;
         # leave_partials: the rows stay unfolded for the optimiser step's first launch (srml_qn_step_mbf)
-        if zcache is not None:
-            zfl, zb, zsc = zcache
-            native.call("srml_logreg_binary4_f32", X.data_ptr(), m, n, X.stride(0), y32.data_ptr(), w.data_ptr(),
-                        0.0, b.data_ptr(), fp, out.data_ptr(), ws.data_ptr() if ws is not None else None,
-                        int(bool(leave_partials and ws is not None)), zfl.data_ptr(), zb.data_ptr(), zsc.data_ptr(),
-                        st)
-        else:
-            native.call("srml_logreg_binary3_f32", X.data_ptr(), m, n, X.stride(0), y32.data_ptr(), w.data_ptr(),
-                        0.0, b.data_ptr(), fp, out.data_ptr(), ws.data_ptr() if ws is not None else None,
-                        int(bool(leave_partials and ws is not None)), st)
+        zc = [t.data_ptr() for t in zcache] if zcache is not None else [None, None, None]
+        native.call("srml_logreg_binary_f32", X.data_ptr(), m, n, X.stride(0), y32.data_ptr(), w.data_ptr(), 0.0,
+                    b.data_ptr(), fp, out.data_ptr(), ws.data_ptr() if ws is not None else None,
+                    int(bool(leave_partials and ws is not None)), *zc, st)
     elif path.startswith("lds_binary"):
         native.call("srml_logreg_binary_lds_" + path[-3:], X.data_ptr(), m, n, X.stride(0), y32.data_ptr(),
                     w.data_ptr(), 0.0, b.data_ptr(), fp, out.data_ptr(), st)
     elif path == "fused_multinomial_f32":
         native.call("srml_mlogit_f32", X.data_ptr(), m, n, X.stride(0), y32.data_ptr(), w.data_ptr(), b.data_ptr(),
                     fp, K, out.data_ptr(), st)
-    elif path == "two_pass_multinomial_f32" or (path == "two_pass_deterministic_f32" and K > 1):
+    elif path in ("two_pass_multinomial_f32", "two_pass_deterministic_f32"):
         _glm_two_pass(X, y32, w.view(K, n), b, 1, 0, out, 1, n, out[K * n:], 1, out[K * n + K:], 0, flag,
                       zc=zcache if path == "two_pass_multinomial_f32" else None)
-    elif path == "two_pass_deterministic_f32":  # binary: one sigmoid model
-        _glm_two_pass(X, y32, w.view(1, n), b, 1, 1, out, 1, n, out[n:], 1, out[n + 1:], 1, flag)
     else:  # pragma: no cover
         raise AssertionError(path)
     return out
@@ -3780,19 +3801,7 @@ SVC_LOSSES = {"hinge": 0, "squared_hinge": 1}
 
 def svc_path(X) -> str:
     """Which pass ``svc_loss_grad`` uses for X (reported by the fit / asserted in tests)."""
-    if _is_csr(X):
-        return "csr_svc" if X.data.is_cuda else "torch-cpu"
-    if not X.is_cuda:
-        return "torch-cpu"
-    n = X.shape[1]
-    f32 = X.dtype == torch.float32
-    if deterministic() and f32:
-        return "two_pass_deterministic_svc_f32"
-    if f32 and n <= 4096:
-        return "fused_svc_f32"
-    if X.dtype in (torch.float32, torch.float64) and n <= 16384:
-        return "lds_svc_" + ("f32" if f32 else "f64")
-    return "two_pass_svc_f32" if f32 else "two_pass_svc_f64"
+    return _binary_path(X, "svc", "two_pass_deterministic_svc_f32")
 
 
 def exact_sum(T: torch.Tensor, bound: Any, dim: int = 0) -> torch.Tensor:
@@ -3896,31 +3905,8 @@ def svc_loss_grad(X, y32: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: t
     elif path.startswith("lds_svc"):
         native.call("srml_svc_loss_grad_lds_" + path[-3:], X.data_ptr(), m, n, X.stride(0), y32.data_ptr(),
                     w.data_ptr(), 0.0, b.data_ptr(), fp, out.data_ptr(), kind, st)
-    elif path == "two_pass_svc_f64":
-        # margins and X^T r on the fp64 MFMA GEMM around the fp64 residual kernel
-        z = dgemm(X, w.view(n, 1))
-        r = zeros((m, 1), dtype=torch.float64, device=dev)  # stays 0 if the done flag skips it
-        native.call("srml_svc_residual_f64", z.data_ptr(), m, 1, 1, y32.data_ptr(), b.data_ptr(), 1, 1,
-                    r.data_ptr(), 1, out[n:].data_ptr(), 1, out[n + 1:].data_ptr(), 1, fp, kind, st)
-        dgemm(X, r, ta=True, beta=1.0, out=out[:n].view(n, 1))
-    elif path in ("two_pass_svc_f32", "two_pass_deterministic_svc_f32"):
-        # margins (srml_xw_f32), the residual kernel, then grad += X^T r (srml_xtv2_f32; ordered
-        # block-row partials on srml_xtv_mfma_det_f32 in deterministic mode)
-        Z = xw(X, w.view(n, 1).float().contiguous())
-        R = torch.empty((m, 1), dtype=torch.float32, device=dev)  # the X^T r pass skips on the flag too
-        args =(Z.data_ptr(), m, 1, Z.stride(0), y32.data_ptr(), b.data_ptr(), 1, 1, R.data_ptr(), 1,
-                out[n:].data_ptr(), 1, out[n + 1:].data_ptr(), 1, fp)
-        if path == "two_pass_deterministic_svc_f32":
-            L = native.lib()
-            dws = torch.empty(max(int(L.srml_logit_residual_ws(m, 1)), int(L.srml_xtv_mfma_ws(m, n, 1)), 1),
-                              dtype=torch.float64, device=dev)
-            native.call("srml_svc_residual_det_f32", *args, dws.data_ptr(), kind, st)
-            native.call("srml_xtv_mfma_det_f32", X.data_ptr(), m, n, X.stride(0), R.data_ptr(), 1, 1, out.data_ptr(),
-                        1, n, fp, dws.data_ptr(), st)
-        else:
-            native.call("srml_svc_residual_f32", *args, kind, st)
-            native.call("srml_xtv2_f32", X.data_ptr(), m, n, X.stride(0), R.data_ptr(), 1, 1, out.data_ptr(), 1, n,
-                        fp, st)
+    elif path in ("two_pass_svc_f32", "two_pass_svc_f64", "two_pass_deterministic_svc_f32"):
+        _binary_two_pass(X, y32, w, b, out, flag, family="svc", kind=(kind,))
     else:  # pragma: no cover
         raise AssertionError(path)
     return out

@@ -8,11 +8,15 @@
 //  * srml_row_sqnorm_f32 — ||x_r||^2 per row (KMeans inertia, kNN/DBSCAN distances).
 //  * srml_logreg_binary_f32 — ONE pass over X per L-BFGS function evaluation:
 //        z_r = x_r · w + b ;  loss += softplus(z_r) - y_r z_r ;  g += (sigmoid(z_r) - y_r) x_r
-//    wave-per-row: the row (up to 256*V floats) is held in registers while its dot product is
-//    reduced with wave64 shuffles, then reused for the gradient update, so X is read exactly
-//    once (the reference's cuML QN path reads it twice: forward GEMV then X^T residual).
-//    w lives in LDS, each wave keeps a private gradient accumulator in registers, waves fold
-//    into LDS and blocks fold into the fp64 output with atomics.
+//    The row stays in registers between its dot product and the gradient update, so X is read
+//    exactly once (the reference's cuML QN path reads it twice: forward GEMV then X^T residual).
+//    Three kernels, chosen by shape and layout (logreg_binary_launch):
+//      narrow    n <= 512, aligned, n % 4 == 0: 16 lanes per row, 4 rows per wave, register ring;
+//      prefetch  1024 < n <= 4096, aligned, n % 4 == 0: each wave owns a column slice of every row,
+//                register ring, optional partial-row epilogue (fold_ws) instead of atomics;
+//      generic   every other n <= 4096 (tail columns, unaligned rows, 512 < n <= 1024): wave per
+//                row, w in LDS, waves fold into LDS and blocks into the fp64 output with atomics.
+//    srml_svc_loss_grad_f32 runs the same kernels with the hinge / squared-hinge row terms.
 #include "common.h"
 #include <stdlib.h>
 
@@ -427,8 +431,9 @@ __device__ __forceinline__ float softplus_f(float z) {
   return z > 0.f ? z + log1pf(__expf(-z)) : log1pf(__expf(z));
 }
 
-
-template <int V, bool REREAD, int LOSS = GLM_LOGISTIC>
+// Generic wave-per-row kernel: the row (up to 256*V floats) is held in registers while its dot
+// product is reduced with wave64 shuffles, then reused for the gradient update.
+template <int V, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restrict__ X, long m, int n, long ld,
                                                             const float* __restrict__ y, const double* __restrict__ w,
                                                             double b_in, const double* __restrict__ bptr,
@@ -463,12 +468,12 @@ __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restr
   const bool vec = ((ld & 3) == 0);
   for (long r = r0 + wid; r < r1; r += 4) {
     const float* row = X + r * ld;
-    floatx4 x[REREAD ? 1 : V];
+    floatx4 x[V];
     double dot = 0.0;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const int c = (v * 64 + lane) * 4;
-      floatx4& xv = x[REREAD ? 0 : v];
+      floatx4& xv = x[v];
       if (vec && c + 3 < n) {
         xv = *reinterpret_cast<const floatx4*>(row + c);
       } else {
@@ -491,22 +496,9 @@ __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restr
     }
     const float rf = (float)res;
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-      floatx4 xv;
-      if (REREAD) {  // second touch of the row hits L1/L2; HBM traffic is unchanged
-        const int c = (v * 64 + lane) * 4;
-        if (vec && c + 3 < n) {
-          xv = *reinterpret_cast<const floatx4*>(row + c);
-        } else {
+    for (int v = 0; v < V; ++v)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) xv[q] = (c + q < n) ? row[c + q] : 0.f;
-        }
-      } else {
-        xv = x[v];
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) g[v][q] = fmaf(rf, xv[q], g[v][q]);
-    }
+      for (int q = 0; q < 4; ++q) g[v][q] = fmaf(rf, x[v][q], g[v][q]);
   }
   // fold the 4 waves' gradients in LDS, then one fp64 atomic per column per block
 #pragma unroll
@@ -522,103 +514,12 @@ __global__ __launch_bounds__(256) void logreg_binary_kernel(const float* __restr
 }
 
 
-// Column-split variant for 1024 < n <= 4096: each of the 4 waves owns a 256*V-column slice of
-// every row (x and its gradient slice stay in registers), the block processes R rows per step;
-// per-row partial margins are exchanged through LDS (double-buffered, one barrier per step).
-template <int V, int R, int LOSS = GLM_LOGISTIC>
-__global__ __launch_bounds__(256, 2) void logreg_binary_split_kernel(const float* __restrict__ X, long m, int n,
-                                                                     long ld, const float* __restrict__ y,
-                                                                     const double* __restrict__ w, double b_in,
-                                                                     const double* __restrict__ bptr,
-                                                                     const int* __restrict__ flag,
-                                                                     double* __restrict__ out, long rows_per_block) {
-  if (flag && *flag) return;
-  const double b = bptr ? *bptr : b_in;
-  __shared__ double part[2][R][4];
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int cbase = wid * 256 * V;
-  double wreg[V][4];
-#pragma unroll
-  for (int v = 0; v < V; ++v)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int c = cbase + (v * 64 + lane) * 4 + q;
-      wreg[v][q] = c < n ? w[c] : 0.0;
-    }
-  floatx4 g[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) g[v] = floatx4{0.f, 0.f, 0.f, 0.f};
-  double gb = 0.0, loss = 0.0;
-  const long r0 = (long)blockIdx.x * rows_per_block;
-  const long r1 = min(m, r0 + rows_per_block);
-  const bool vec = ((ld & 3) == 0);
-  int buf = 0;
-  for (long rb = r0; rb < r1; rb += R) {
-    floatx4 x[R][V];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const long r = rb + i;
-      double dot = 0.0;
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const int c = cbase + (v * 64 + lane) * 4;
-        // branch-free: clamped row / column, out-of-range lanes multiply by zero weights
-        // (wreg is 0 beyond n) and rows past r1 are dropped after the reduction
-        const float* row = X + (r < r1 ? r : r1 - 1) * ld;
-        floatx4 xv;
-        if (vec) {
-          xv = *reinterpret_cast<const floatx4*>(row + (c + 3 < n ? c : 0));
-          if (c + 3 >= n) xv = floatx4{0.f, 0.f, 0.f, 0.f};
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) xv[q] = row[c + q < n ? c + q : 0] * (c + q < n ? 1.f : 0.f);
-        }
-        x[i][v] = xv;
-        dot = fma((double)xv[0], wreg[v][0], fma((double)xv[1], wreg[v][1],
-              fma((double)xv[2], wreg[v][2], fma((double)xv[3], wreg[v][3], dot))));
-      }
-      dot = wave_sum(dot);
-      if (lane == 0) part[buf][i][wid] = dot;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const long r = rb + i;
-      if (r >= r1) break;
-      const double z = part[buf][i][0] + part[buf][i][1] + part[buf][i][2] + part[buf][i][3] + b;
-      const double yr = (double)y[r];
-      double res, lt;
-      binary_terms<LOSS>(z, yr, res, lt);
-      if (wid == 0 && lane == 0) {
-        loss += lt;
-        gb += res;
-      }
-      const float rf = (float)res;
-#pragma unroll
-      for (int v = 0; v < V; ++v)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[v][q] = fmaf(rf, x[i][v][q], g[v][q]);
-    }
-    buf ^= 1;
-  }
-#pragma unroll
-  for (int v = 0; v < V; ++v)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int c = cbase + (v * 64 + lane) * 4 + q;
-      if (c < n) atomicAdd(&out[c], (double)g[v][q]);
-    }
-  if (wid == 0 && lane == 0) {
-    atomicAdd(&out[n], gb);
-    atomicAdd(&out[n + 1], loss);
-  }
-}
-
-// Column-split + prefetch variant: like logreg_binary_split_kernel, but the next R-row batch is
-// loaded into a second register set while the current batch's margins are reduced / exchanged
-// through LDS and its gradient is accumulated, so each wave keeps 2 * R * V * 1 KiB of X in flight
-// across the per-batch barrier (the kernel is HBM-latency bound, not VALU bound).
+// Column-split + prefetch kernel for 1024 < n <= 4096: each of the 4 waves owns a 256*V-column
+// slice of every row (x and its gradient slice stay in registers) and the block processes LR_PF_R
+// rows per step; per-row partial margins are exchanged through LDS (double-buffered, one barrier
+// per step). Batches are loaded LR_PF_D steps ahead of their use into a register ring, so each
+// wave keeps LR_PF_D * LR_PF_R * V KiB of X in flight across the per-batch barrier (the kernel is
+// HBM-latency bound, not VALU bound).
 // Line-search margin cache (zfl != null; the optimiser's flag block, see qn.hip F_ZMODE): along a
 // search direction the margins are linear in the step, z(a) = z0 + (a / a1) (z(a1) - z0), so once
 // a full evaluation at a1 is rejected, the backtracking trials need only the loss from the two
@@ -674,7 +575,11 @@ __device__ __forceinline__ void lr_margin_only(long m, int n, const float* __res
   }
 }
 
-template <int V, int R, int D, bool NT = false, int LOSS = GLM_LOGISTIC>
+constexpr int LR_PF_R = 1;       // rows per batch
+constexpr int LR_PF_D = 3;       // batches loaded ahead
+constexpr bool LR_PF_NT = true;  // X streams through non-temporal loads: +2%
+
+template <int V, int LOSS = GLM_LOGISTIC>
 __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* __restrict__ X, long m, int n, long ld,
                                                                   const float* __restrict__ y,
                                                                   const double* __restrict__ w, double b_in,
@@ -684,6 +589,7 @@ __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* _
                                                                   float* __restrict__ ws, const int* __restrict__ zfl,
                                                                   double* __restrict__ zb,
                                                                   const double* __restrict__ zsc) {
+  constexpr int R = LR_PF_R, D = LR_PF_D;
   if (flag && *flag) return;
   const double b = bptr ? *bptr : b_in;
   __shared__ double part[2][R][4];
@@ -722,8 +628,8 @@ __global__ __launch_bounds__(256, 2) void logreg_binary_pf_kernel(const float* _
       const float* row = X + r * ld;
 #pragma unroll
       for (int v = 0; v < V; ++v)
-        x[i][v] = NT ? __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(row + coff[v]))
-                     : *reinterpret_cast<const floatx4*>(row + coff[v]);
+        x[i][v] = LR_PF_NT ? __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(row + coff[v]))
+                           : *reinterpret_cast<const floatx4*>(row + coff[v]);
     }
   };
   int buf = 0;
@@ -996,10 +902,13 @@ __global__ __launch_bounds__(256) void fold_rows_kernel(const float* __restrict_
   }
 }
 
+// Blocks of the generic and prefetching kernels (the narrow kernel sizes its own grid in the
+// launcher) and of the partial-row workspace. ~>= 160 rows per block: each block pays a w load and
+// an n-wide flush, so small shards (the per-rank rows of a multi-GPU fit) want fewer blocks. 125k
+// rows: 768 blocks = 3 per CU, all resident at once (149 VGPRs), 0.310 ms per evaluation against
+// 0.328 at 512 blocks, 0.331 at 1024 and 0.345 at 1536; 1M rows: 2048 is best.
+// SRML_LOGREG_BLOCKS overrides the count.
 static long logreg_grid(long m) {
-  // ~>= 160 rows per block: each block pays a w load and an n-wide flush, so small shards (the
-  // per-rank rows of a multi-GPU fit) want fewer blocks (125k rows: 768 blocks = 3 per CU, all
-  // resident at once (149 VGPRs); 1M rows: 2048)
   static const long blocks_env = getenv("SRML_LOGREG_BLOCKS") ? atol(getenv("SRML_LOGREG_BLOCKS")) : 0;
   long blocks = blocks_env;
   if (blocks <= 0) {
@@ -1013,11 +922,15 @@ static long logreg_grid(long m) {
 }
 
 // The prefetching column-split kernel (the only one with a partial-row epilogue) runs for this
-// shape / layout: 1024 < n <= 4096, 16-B aligned rows, n % 4 == 0, SRML_LOGREG_SPLIT == 2.
+// shape / layout: 1024 < n <= 4096, 16-B aligned rows, n % 4 == 0 (it has no tail columns).
 static bool logreg_pf_eligible(int n, long ld, const void* X) {
-  static const int split = getenv("SRML_LOGREG_SPLIT") ? atoi(getenv("SRML_LOGREG_SPLIT")) : 2;
-  return split == 2 && n > 1024 && n <= 4096 && (n & 3) == 0 && (ld & 3) == 0 &&
-         (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  return n > 1024 && n <= 4096 && (n & 3) == 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+}
+
+// The narrow kernel: n <= 512, same layout (SRML_LOGREG_NARROW=0: the generic kernel instead).
+static bool logreg_narrow_eligible(int n, long ld, const void* X) {
+  static const int narrow = getenv("SRML_LOGREG_NARROW") ? atoi(getenv("SRML_LOGREG_NARROW")) : 1;
+  return narrow && n <= 512 && (n & 3) == 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
 }
 
 static bool logreg_fold_enabled() {
@@ -1026,7 +939,7 @@ static bool logreg_fold_enabled() {
   return fold != 0;
 }
 
-// Floats of the partial-row workspace srml_logreg_binary3_f32 needs for X (m x n, row stride ld)
+// Floats of the partial-row workspace srml_logreg_binary_f32 needs for X (m x n, row stride ld)
 // — 0 unless the evaluation of exactly this operand writes partial rows (the consumer may then
 // fold them; any other kernel flushes into `out` and would leave a workspace unwritten).
 SRML_API long srml_logreg_fold_ws(long m, int n, long ld, const void* X) {
@@ -1037,54 +950,20 @@ SRML_API long srml_logreg_fold_ws(long m, int n, long ld, const void* X) {
 // Partial rows (= blocks) the workspace holds for m rows; row stride ((n + 3) & ~3) + 4 floats.
 SRML_API long srml_logreg_fold_parts(long m) { return m <= 0 ? 0 : logreg_grid(m); }
 
-// LOSS: the per-row terms (common.h binary_terms); every kernel choice below is the same for all losses.
-template <int LOSS = GLM_LOGISTIC>
-static int logreg_binary_launch(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
-                                const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
-                                hipStream_t stream, const int* zfl = nullptr, double* zb = nullptr,
-                                const double* zsc = nullptr);
-
-// b: intercept by value, or (bptr != null) read on the device; flag (optional): skip when *flag != 0
-SRML_API int srml_logreg_binary2_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
-                                     const double* bptr, const int* flag, double* out, hipStream_t stream) {
-  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, nullptr, 0, stream);
-}
-
-// Same with the caller's partial-row workspace (srml_logreg_fold_ws floats, owned by ONE fit: the
-// block partials and their fold are two launches, so interleaved fits need separate workspaces).
-// leave != 0: the rows are NOT folded into `out` here — the consumer (the optimiser step's first
-// launch, srml_qn_step_mbf) folds them itself.
-SRML_API int srml_logreg_binary3_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
-                                     const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
-                                     hipStream_t stream) {
-  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
-}
-
-// Same with the optimiser's line-search margin cache (see logreg_binary_pf_kernel): zfl = the QN
-// flag block, zb = 2 m doubles of margins, zsc = the QN scalars. Only the prefetching column-split
-// kernel implements it: -2 for any other shape (the caller checks srml_logreg_fold_ws > 0 first).
-static bool logreg_narrow_eligible(int n, long ld, const void* X) {
-  static const int narrow = getenv("SRML_LOGREG_NARROW") ? atoi(getenv("SRML_LOGREG_NARROW")) : 1;
-  return narrow && n <= 512 && (n & 3) == 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-}
-
 // Whether the evaluation of X (m x n, row stride ld) runs a kernel with the line-search margin
 // cache (the narrow n <= 512 or the prefetching 1024 < n <= 4096 kernel).
 SRML_API int srml_logreg_zcache_ok(long m, int n, long ld, const void* X) {
   return m > 0 && (logreg_narrow_eligible(n, ld, X) || logreg_pf_eligible(n, ld, X)) ? 1 : 0;
 }
 
-SRML_API int srml_logreg_binary4_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
-                                     const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
-                                     const int* zfl, double* zb, const double* zsc, hipStream_t stream) {
-  if (m > 0 && !srml_logreg_zcache_ok(m, n, ld, X)) return -2;
-  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream, zfl, zb, zsc);
-}
-
+// One evaluation, kernel chosen by shape and layout: narrow, prefetching, else generic (-2 beyond
+// n = 4096: the caller uses the two-pass path). LOSS: the per-row terms (common.h binary_terms);
+// every kernel choice is the same for all losses, except the narrow ring depth noted below.
+// Arguments: see srml_logreg_binary_f32.
 template <int LOSS>
 static int logreg_binary_launch(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                 const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
-                                hipStream_t stream, const int* zfl, double* zb, const double* zsc) {
+                                const int* zfl, double* zb, const double* zsc, hipStream_t stream) {
   if (m <= 0) return 0;
   if (LOSS != GLM_LOGISTIC && zfl) return -2;  // the line-search margin cache is logistic-only
   if (zfl && !logreg_pf_eligible(n, ld, X) && !logreg_narrow_eligible(n, ld, X)) return -2;
@@ -1117,77 +996,32 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
 #undef SRML_LR_NARROW
     return srml_status();
   }
-  // grid sweep (tools/lr_small_sweep.sh): 125k rows 768 blocks 0.310 ms, 1024 0.331, 1536 0.345,
-  // 512 0.328; 1M rows: 2048 best
   const long blocks = logreg_grid(m);
   long rpb = (m + blocks - 1) / blocks;
   if (rpb < 16) rpb = 16;
-  int V = (n + 255) / 256;
-  const size_t vpad = V <= 1 ? 1 : V <= 2 ? 2 : V <= 4 ? 4 : V <= 8 ? 8 : V <= 12 ? 12 : 16;
-  size_t lds = 256 * vpad * (sizeof(double) + sizeof(float));
   dim3 grid((unsigned)blocks), blk(256);
-  static const int split = getenv("SRML_LOGREG_SPLIT") ? atoi(getenv("SRML_LOGREG_SPLIT")) : 2;
-  // prefetching column-split kernel: needs 16-B aligned rows and n % 4 == 0 (no tail columns)
   if (logreg_pf_eligible(n, ld, X)) {
-    static const int rsel = getenv("SRML_LOGREG_R") ? atoi(getenv("SRML_LOGREG_R")) : 1;
-    static const int dsel = getenv("SRML_LOGREG_D") ? atoi(getenv("SRML_LOGREG_D")) : 3;
-    static const int nt = getenv("SRML_LOGREG_NT") ? atoi(getenv("SRML_LOGREG_NT")) : 1;  // nontemporal X stream: +2%
-    const int VS = (n + 1023) / 1024;
+    const int VS = (n + 1023) / 1024;  // 2 .. 4: KiB of a row per wave
     // partial-row epilogue + fold kernel when the caller passed a workspace
     const long wst = ((n + 3) & ~3) + 4;
     float* fws = logreg_fold_enabled() ? fold_ws : nullptr;
-#define SRML_LR_PF(VV, RR, DD)                                                                              \
-    hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, RR, DD, false, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
-                       flag, out, rpb, fws, zfl, zb, zsc)
-#define SRML_LR_PF_V(RR, DD) \
-    do { if (VS == 2) SRML_LR_PF(2, RR, DD); else if (VS == 3) SRML_LR_PF(3, RR, DD); else SRML_LR_PF(4, RR, DD); } while (0)
-    if (rsel == 2 && dsel == 1) SRML_LR_PF_V(2, 1);
-    else if (rsel == 2) SRML_LR_PF_V(2, 2);
-    else if (dsel == 1) SRML_LR_PF_V(1, 1);
-    else if (dsel == 3 && nt) {
-#define SRML_LR_PF_NT(VV)                                                                                        \
-  hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, 1, 3, true, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
-                     flag, out, rpb, fws, zfl, zb, zsc)
-      if (VS == 2) SRML_LR_PF_NT(2);
-      else if (VS == 3) SRML_LR_PF_NT(3);
-      else SRML_LR_PF_NT(4);
-#undef SRML_LR_PF_NT
-    }
-    else if (dsel == 3) SRML_LR_PF_V(1, 3);
-    else SRML_LR_PF_V(1, 2);
+#define SRML_LR_PF(VV)                                                                                       \
+  hipLaunchKernelGGL((logreg_binary_pf_kernel<VV, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, flag, out, \
+                     rpb, fws, zfl, zb, zsc)
+    if (VS == 2) SRML_LR_PF(2);
+    else if (VS == 3) SRML_LR_PF(3);
+    else SRML_LR_PF(4);
+#undef SRML_LR_PF
     if (fws && !leave)
       hipLaunchKernelGGL(fold_rows_kernel, dim3(ceil_div(n, 64) + 1), dim3(256), 0, stream, fws, (int)blocks, wst, n,
                          out, flag);
     return srml_status();
   }
-  if (split == 1 && n > 1024 && n <= 4096) {
-    static const int rsel = getenv("SRML_LOGREG_R") ? atoi(getenv("SRML_LOGREG_R")) : 4;
-    const int VS = (n + 1023) / 1024;
-#define SRML_LR_SPLIT(VV, RR)                                                                                      \
-    hipLaunchKernelGGL((logreg_binary_split_kernel<VV, RR, LOSS>), grid, blk, 0, stream, X, m, n, ld, y, w, b, bptr, \
-                       flag, out, rpb)
-    if (rsel == 8) {
-      if (VS == 1) SRML_LR_SPLIT(1, 8); else if (VS == 2) SRML_LR_SPLIT(2, 8);
-      else if (VS == 3) SRML_LR_SPLIT(3, 8); else SRML_LR_SPLIT(4, 8);
-    } else if (rsel == 2) {
-      if (VS == 1) SRML_LR_SPLIT(1, 2); else if (VS == 2) SRML_LR_SPLIT(2, 2);
-      else if (VS == 3) SRML_LR_SPLIT(3, 2); else SRML_LR_SPLIT(4, 2);
-    } else {
-      if (VS == 1) SRML_LR_SPLIT(1, 4); else if (VS == 2) SRML_LR_SPLIT(2, 4);
-      else if (VS == 3) SRML_LR_SPLIT(3, 4); else SRML_LR_SPLIT(4, 4);
-    }
-    return srml_status();
-  }
-  const int reread = 0;
-#define SRML_LR_LAUNCH(VV)                                                                                       \
-  do {                                                                                                           \
-    if (reread)                                                                                                  \
-      hipLaunchKernelGGL((logreg_binary_kernel<VV, true, LOSS>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, \
-                         flag, out, rpb);                                                                        \
-    else                                                                                                         \
-      hipLaunchKernelGGL((logreg_binary_kernel<VV, false, LOSS>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, \
-                         flag, out, rpb);                                                                        \
-  } while (0)
+  const int V = (n + 255) / 256;
+  const size_t vpad = V <= 1 ? 1 : V <= 2 ? 2 : V <= 4 ? 4 : V <= 8 ? 8 : V <= 12 ? 12 : 16;
+  const size_t lds = 256 * vpad * (sizeof(double) + sizeof(float));
+#define SRML_LR_LAUNCH(VV)                                                                                        \
+  hipLaunchKernelGGL((logreg_binary_kernel<VV, LOSS>), grid, blk, lds, stream, X, m, n, ld, y, w, b, bptr, flag, out, rpb)
   if (V <= 1) SRML_LR_LAUNCH(1);
   else if (V <= 2) SRML_LR_LAUNCH(2);
   else if (V <= 4) SRML_LR_LAUNCH(4);
@@ -1195,20 +1029,38 @@ static int logreg_binary_launch(const float* X, long m, int n, long ld, const fl
   else if (V <= 12) SRML_LR_LAUNCH(12);
   else if (V <= 16) SRML_LR_LAUNCH(16);
   else return -2;  // n > 4096: caller uses the two-pass GEMV path
+#undef SRML_LR_LAUNCH
   return srml_status();
 }
 
+// The binary logistic evaluation; every pointer from `bptr` on may be null.
+//   b / bptr         intercept by value, or (bptr != null) read on the device;
+//   flag             the launch skips when *flag != 0;
+//   fold_ws, leave   the caller's partial-row workspace (srml_logreg_fold_ws floats, owned by ONE
+//                    fit: the block partials and their fold are two launches, so interleaved fits
+//                    need separate workspaces). leave != 0: the rows are NOT folded into `out`
+//                    here — the consumer (the optimiser step's first launch, srml_qn_step_mbf)
+//                    folds them itself;
+//   zfl, zb, zsc     the optimiser's line-search margin cache (see logreg_binary_pf_kernel): the QN
+//                    flag block, 2 m doubles of margins, the QN scalars. Only the narrow and the
+//                    prefetching kernel implement it: -2, and nothing launched, for any other
+//                    shape (the caller checks srml_logreg_zcache_ok first).
 SRML_API int srml_logreg_binary_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
-                                    double* out, hipStream_t stream) {
-  return srml_logreg_binary2_f32(X, m, n, ld, y, w, b, nullptr, nullptr, out, stream);
+                                    const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
+                                    const int* zfl, double* zb, const double* zsc, hipStream_t stream) {
+  return logreg_binary_launch<GLM_LOGISTIC>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, zfl, zb, zsc, stream);
 }
 
-// LinearSVC data term: the same kernels and internal dispatch as srml_logreg_binary3_f32 with the
+// LinearSVC data term: the same kernels and internal dispatch as srml_logreg_binary_f32 with the
 // hinge (loss 0) or squared-hinge (loss 1) per-row terms; out = [grad w (n) | grad b | loss sum].
 SRML_API int srml_svc_loss_grad_f32(const float* X, long m, int n, long ld, const float* y, const double* w, double b,
                                     const double* bptr, const int* flag, double* out, float* fold_ws, int leave,
                                     int loss, hipStream_t stream) {
-  if (loss == 0) return logreg_binary_launch<GLM_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
-  if (loss == 1) return logreg_binary_launch<GLM_SQ_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, stream);
+  if (loss == 0)
+    return logreg_binary_launch<GLM_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, nullptr, nullptr,
+                                           nullptr, stream);
+  if (loss == 1)
+    return logreg_binary_launch<GLM_SQ_HINGE>(X, m, n, ld, y, w, b, bptr, flag, out, fold_ws, leave, nullptr, nullptr,
+                                              nullptr, stream);
   return -2;
 }

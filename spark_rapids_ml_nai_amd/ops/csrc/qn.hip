@@ -1326,7 +1326,7 @@ __global__ __launch_bounds__(MB_T) void qn_mb1f_kernel(QnArgs A, double* __restr
 }
 
 // One optimiser step of a one-rank binary fit as four launches with the evaluation's fold in K1:
-// fws = srml_logreg_binary3_f32's workspace left unfolded (leave = 1), parts rows of wst floats.
+// fws = srml_logreg_binary_f32's workspace left unfolded (leave = 1), parts rows of wst floats.
 SRML_API int srml_qn_step_mbf(const QnArgs* a, double* scratch, const float* fws, int parts, long wst,
                               hipStream_t stream) {
   if (a->M < 1 || a->M > QN_MMAX || a->N <= 0 || !scratch || !fws) return (int)hipErrorInvalidValue;

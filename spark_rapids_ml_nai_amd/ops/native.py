@@ -46,10 +46,7 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_sign_flip_f64": (_P, _I, _I, _L, _P),
     "srml_xtv_f32": (_P, _L, _I, _L, _P, _I, _L, _P, _P),
     "srml_row_sqnorm_f32": (_P, _L, _I, _L, _P, _P),
-    "srml_logreg_binary_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P),
-    "srml_logreg_binary2_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _P),
-    "srml_logreg_binary3_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _P, _I, _P),
-    "srml_logreg_binary4_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P, _P),
+    "srml_logreg_binary_f32": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P, _P),
     "srml_logreg_fold_parts": (_L,),
     "srml_logreg_fold_ws": (_L, _I, _L, _P),
     "srml_logreg_zcache_ok": (_L, _I, _L, _P),

@@ -7,9 +7,8 @@ panels), dtype, CSR or dense, ``SRML_LOGREG_FUSED`` and ``SRML_DETERMINISTIC``; 
 own row grouping. The cases here sit on both sides of each threshold, below one block / one row
 group, at m < K, with empty and dense CSR rows, and in four margin regimes (benign, wide,
 saturated-correct, extreme) with mixed and single-class labels. Only the default dispatch is tested:
-the knobs read once per process (``SRML_LOGREG_SPLIT`` / ``NARROW`` / ``R`` / ``D`` / ``NT`` /
-``BLOCKS`` / ``FOLD``) would need a child process each; the line-search margin cache stays with the
-fit-level tests in ``test_qn.py``.
+the knobs read once per process (``SRML_LOGREG_NARROW`` / ``BLOCKS`` / ``FOLD``) would need a child
+process each; the line-search margin cache stays with the fit-level tests in ``test_qn.py``.
 
 Oracle. The reference is computed on the CPU from the inputs exactly as the device sees them
 (``X.double()`` of the fp32 / fp64 tensor, fp64 W and b): in 80-bit ``longdouble`` for the fp64

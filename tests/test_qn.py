@@ -432,6 +432,33 @@ def test_logreg_margin_only_evaluation_matches_full(gpu_device, n):
 
 
 @pytest.mark.gpu
+def test_logreg_margin_cache_refused_without_a_cache_kernel(gpu_device):
+    """A margin cache passed for a shape that runs the generic kernel (512 < n <= 1024: neither
+    narrow nor prefetching) is refused by the launcher: the call raises and nothing is launched,
+    so ``out`` and the margin buffers keep what they held."""
+    from spark_rapids_ml_nai_amd import ops
+
+    rng = np.random.default_rng(22)
+    m, n = 65, 516
+    X = torch.from_numpy(rng.standard_normal((m, n)).astype(np.float32)).to(gpu_device)
+    y = torch.from_numpy((rng.random(m) > 0.4).astype(np.float32)).to(gpu_device)
+    assert ops.logistic_path(X, 1) == "fused_binary_f32" and not ops.logreg_zcache_ok(X)
+    w = torch.from_numpy(rng.standard_normal(n) * 0.05).to(gpu_device)
+    b = torch.tensor([0.3], dtype=torch.float64, device=gpu_device)
+    fl = torch.zeros(16, dtype=torch.int32, device=gpu_device)
+    zb = torch.full((2 * m,), 7.0, dtype=torch.float64, device=gpu_device)
+    sc = torch.zeros(8, dtype=torch.float64, device=gpu_device)
+    out = torch.full((n + 2,), -3.0, dtype=torch.float64, device=gpu_device)
+    with pytest.raises(RuntimeError, match="srml_logreg_binary_f32"):
+        ops.logistic_loss_grad(X, y, w, b, 1, out, zcache=(fl, zb, sc))
+    torch.cuda.synchronize(gpu_device)
+    assert bool((out == -3.0).all()) and bool((zb == 7.0).all())
+    # the same shape without the cache runs
+    ops.logistic_loss_grad(X, y, w, b, 1, out)
+    assert bool((out != -3.0).all())
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n,classes", [(1200, 2), (256, 2), (300, 4), (200, 11), (2000, 9)])  # last: N > 16384
 def test_logistic_fit_margin_cache_matches_full_evaluations(gpu_device, monkeypatch, n, classes):
     """A fit whose rejected line-search trials are margins-only evaluations (binary: narrow /

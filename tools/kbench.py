@@ -60,7 +60,7 @@ def main():
         res["logreg"] = {"ms": t, "TB/s": gb / t}
     if want("svc"):
         # one evaluation of the LinearSVC data term (ops.svc_loss_grad) for both losses against the
-        # logistic one (srml_logreg_binary3_f32: the same kernel with more arithmetic per row) in the
+        # logistic one (srml_logreg_binary_f32: the same kernel with more arithmetic per row) in the
         # same session: the three alternate for `rounds` rounds of 10 timed calls; ms = the median
         # round, spread = (max - min) / median over the rounds
         y = (torch.rand(a.m, device=dev) > 0.5).float()
