@@ -74,8 +74,41 @@ def refine_sorted(Q: torch.Tensor, I: torch.Tensor, idx: torch.Tensor) -> Tuple[
     return d2, idx.gather(1, j)
 
 
-def knn_graph(Q: torch.Tensor, I: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Exact (euclidean distances [mq, k] fp32, indices [mq, k] int64) of Q's rows in I."""
+SPARSE_KINDS = ("euclidean", "hellinger", "jaccard")  # metric kinds the CSR search serves
+
+
+def is_csr(X: Any) -> bool:
+    """A CSR row set (``core.base.CSR`` or prepared ``ops.CSRRows``) instead of a dense tensor."""
+    return isinstance(X, ops.CSRRows) or (hasattr(X, "indptr") and hasattr(X, "indices"))
+
+
+def sparse_kind(metric: str) -> str:
+    """The metric kind of the CSR search; ``ValueError`` for a kind it does not serve."""
+    name = "euclidean" if is_euclidean(metric) else str(metric).lower()
+    if name not in SPARSE_KINDS:
+        raise ValueError("metric kind %r has no sparse kNN graph (CSR rows: %s)" % (metric, ", ".join(SPARSE_KINDS)))
+    return name
+
+
+def knn_graph_csr(Q: Any, I: Any, k: int, metric: str = "euclidean") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact (distances [mq, k] fp32, indices [mq, k] int64) between two CSR row sets (``ops.csr_knn``).
+    Euclidean: the expanded-form keys select, the distances are re-computed in direct form
+    (``ops.csr_refine_sort``); Hellinger and Jaccard keys are the distances."""
+    kind = sparse_kind(metric)
+    if kind != "euclidean":
+        return ops.csr_knn(Q, I, k, kind)
+    Qp = ops.csr_prepare(Q, "sqeuclidean")
+    Ip = Qp if I is Q else ops.csr_prepare(I, "sqeuclidean")
+    _, idx = ops.csr_knn(Qp, Ip, k, "sqeuclidean")
+    d2, idx = ops.csr_refine_sort(Qp, Ip, idx)
+    return torch.sqrt(d2.clamp_min(0)), idx
+
+
+def knn_graph(Q: Any, I: Any, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact (euclidean distances [mq, k] fp32, indices [mq, k] int64) of Q's rows in I (dense
+    tensors, or two CSR row sets)."""
+    if is_csr(I):
+        return knn_graph_csr(Q, I, k)
     _, idx = ops.knn(Q, I, k, inorm=ops.row_sqnorm(I))
     d2, idx = refine_sorted(Q, I, idx)
     return torch.sqrt(d2.clamp_min(0)), idx
@@ -94,12 +127,17 @@ def knn_graph_metric(Q: torch.Tensor, I: torch.Tensor, k: int, metric: str,
     return ops.knn_metric(Q, I, k, metric, p)
 
 
-def knn_graph_brute(X: torch.Tensor, k: int, ctx: Any = None, metric: str = "euclidean",
+def knn_graph_brute(X: Any, k: int, ctx: Any = None, metric: str = "euclidean",
                     p: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact all-points graph; distributed, each rank queries its row block against the replicated
-    rows and the blocks are all-gathered. A non-Euclidean ``metric`` runs ``knn_graph_metric``."""
+    rows and the blocks are all-gathered. A non-Euclidean ``metric`` runs ``knn_graph_metric``; a CSR
+    ``X`` runs ``knn_graph_csr`` (the rank's block keeps absolute offsets into the replicated CSR)."""
     lo, hi = row_split(X.shape[0], ctx)
-    if is_euclidean(metric):
+    if is_csr(X):
+        kind = sparse_kind(metric)
+        P = ops.csr_prepare(X, "sqeuclidean" if kind == "euclidean" else kind)
+        dist, idx = knn_graph_csr(P.rows(lo, hi), P, k, kind)
+    elif is_euclidean(metric):
         dist, idx = knn_graph(X[lo:hi], X, k)
     else:
         dist, idx = knn_graph_metric(X[lo:hi], X, k, metric, p)
@@ -435,7 +473,7 @@ def knn_graph_ivf(X: torch.Tensor, k: int, nlist: Optional[int] = None, nprobe: 
     return dist, out_i
 
 
-def build_knn_graph(X: torch.Tensor, k: int, build_algo: str = "auto", build_kwds: Optional[dict] = None,
+def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Optional[dict] = None,
                     seed: int = 0, ctx: Any = None, list_order: bool = False, phases: Optional[dict] = None,
                     metric: str = "euclidean", p: float = 2.0) -> Any:
     """(dist, idx); with ``list_order`` (dist, idx, order) where ``order`` is None unless the
@@ -444,9 +482,24 @@ def build_knn_graph(X: torch.Tensor, k: int, build_algo: str = "auto", build_kwd
     ``metric`` / ``p``: a metric of ``ops.pairwise_dist`` is served by the exact chunked search
     only: ``auto`` and ``brute_force_knn`` run it at ANY row count, which is O(N^2 n) work (the
     100k-row switch to IVF lists applies to the Euclidean family alone); the IVF lists and the
-    NN-descent re-scoring are Euclidean throughout, so ``ivf`` / ``nn_descent`` raise."""
+    NN-descent re-scoring are Euclidean throughout, so ``ivf`` / ``nn_descent`` raise.
+
+    A CSR ``X`` (metric kinds ``euclidean`` — the caller may have unit-scaled the rows for cosine —
+    ``hellinger`` and ``jaccard``) is served by the exact CSR search only, at any row count too."""
     algo = (build_algo or "auto").lower()
-    if not is_euclidean(metric):
+    if is_csr(X):
+        sparse_kind(metric)
+        if algo in ("ivf", "ivfflat", "ivf_flat", "nn_descent"):
+            raise ValueError("build_algo %r builds graphs of dense rows only; sparse (CSR) rows need build_algo "
+                             "'auto' or 'brute_force_knn' (the exact search)" % (build_algo,))
+        if algo == "auto":
+            algo = "brute_force_knn"
+        if X.shape[0] > BRUTE_MAX_ROWS:
+            from ..utils.log import get_logger
+
+            get_logger("knn_graph").info("sparse kNN graph of %d rows: the CSR search is exact and O(N^2) (no "
+                                         "approximate builder for sparse rows)", X.shape[0])
+    elif not is_euclidean(metric):
         if algo in ("ivf", "ivfflat", "ivf_flat", "nn_descent"):
             raise ValueError("build_algo %r builds Euclidean graphs only; metric %r needs build_algo 'auto' or "
                              "'brute_force_knn' (the exact search)" % (build_algo, metric))

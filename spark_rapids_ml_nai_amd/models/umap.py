@@ -143,6 +143,31 @@ def _metric_rows(Xf: torch.Tensor, pre: Optional[str]) -> torch.Tensor:
     return Xf / Xf.norm(dim=1, keepdim=True).clamp_min(1e-30)
 
 
+SPARSE_METRICS = ("euclidean", "l2", "sqeuclidean", "cosine", "hellinger", "jaccard")
+
+
+def check_sparse_metric(metric: Any, kind: str, pre: Optional[str]) -> None:
+    """``ValueError`` for a metric the CSR route does not serve (correlation centres the rows, which
+    destroys sparsity; the VALU metrics have no CSR kernel): nothing is densified silently."""
+    if pre == "centred_unit" or kind not in ("euclidean", "hellinger", "jaccard"):
+        raise ValueError("metric %r is not supported on sparse (CSR) input; supported: %s. Fit with "
+                         "enable_sparse_data_optim=False to densify the rows." % (metric, ", ".join(SPARSE_METRICS)))
+
+
+def _sparse_metric_rows(X: Any, metric: Any, kind: str, pre: Optional[str]) -> Any:
+    """CSR rows as the sparse graph builder reads them: fp32 values, scaled by
+    1 / max(||row||, 1e-30) for cosine (``_metric_rows``'s rule, zero rows included)."""
+    from ..core.base import CSR
+
+    check_sparse_metric(metric, kind, pre)
+    data = X.data.float()
+    if pre == "unit":
+        m = X.shape[0]
+        norm = torch.sqrt(ops._csr_block_row_sums(X.indptr, (data * data).contiguous(), m)).float().clamp_min(1e-30)
+        data = data / torch.repeat_interleave(norm, X.indptr[1:] - X.indptr[:-1])
+    return CSR(indptr=X.indptr, indices=X.indices, data=data.contiguous(), shape=(int(X.shape[0]), int(X.shape[1])))
+
+
 def _metric_dist(dist: torch.Tensor, post: Optional[str]) -> torch.Tensor:
     if post == "half_square":
         return 0.5 * dist * dist  # 1 - cos for unit rows
@@ -570,8 +595,10 @@ def _n_epochs_default(n: int) -> int:
     return 500 if n <= 10000 else 200
 
 
-def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] = None, ctx: Any = None) -> np.ndarray:
-    """Embedding (N x n_components, float32) of the rows of X.
+def umap_fit(X: Any, params: Dict[str, Any], y: Optional[torch.Tensor] = None, ctx: Any = None) -> np.ndarray:
+    """Embedding (N x n_components, float32) of the rows of X: a dense tensor, or a device ``CSR``
+    (``core.base.CSR``) whose rows only the kNN graph reads (``knn_graph.knn_graph_csr``: exact, the
+    metrics of ``SPARSE_METRICS``); everything after the graph works on (dist, idx).
 
     ``ctx`` with ``world_size > 1`` (X replicated on every rank): every phase shards over the
     ranks — the IVF quantiser's Lloyd iterations (1/W of the training sample each, sums
@@ -603,12 +630,18 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
     if a is None or b is None:
         a, b = find_ab_params(float(params.get("spread", 1.0)), float(params.get("min_dist", 0.1)))
     kind, pre_map, post_map, mink_p = resolve_metric(metric, params.get("metric_kwds"))
-    Xf = _metric_rows(X.float().contiguous(), pre_map)
+    from .knn_graph import is_csr
+
+    dev = X.device
     pre = params.get("precomputed_knn")
+    if is_csr(X):
+        Xf = _sparse_metric_rows(X, metric, kind, pre_map) if pre is None else None
+    else:
+        Xf = _metric_rows(X.float().contiguous(), pre_map)
     order = None  # graph row i is original row order[i] (IVF list order), None: original order
     if pre is not None:
-        idx = torch.as_tensor(np.asarray(pre[0]), dtype=torch.int64, device=X.device)[:, :k]
-        dist = torch.as_tensor(np.asarray(pre[1]), dtype=torch.float32, device=X.device)[:, :k]
+        idx = torch.as_tensor(np.asarray(pre[0]), dtype=torch.int64, device=dev)[:, :k]
+        dist = torch.as_tensor(np.asarray(pre[1]), dtype=torch.float32, device=dev)[:, :k]
     else:
         from .knn_graph import build_knn_graph
 
@@ -619,18 +652,18 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
         dist = _metric_dist(dist, post_map)
     lc = float(params.get("local_connectivity", 1.0))
     mix = float(params.get("set_op_mix_ratio", 1.0))
-    if X.is_cuda:  # fused kernels: smooth_knn_dist + membership, then the kNN-structured union
+    if dev.type == "cuda":  # fused kernels: smooth_knn_dist + membership, then the kNN-structured union
         _, _, w = ops.umap_smooth_knn(dist, idx, float(k), local_connectivity=lc, self_rows=True)
         rows, cols, vals = ops.umap_fuzzy_union_knn(idx, w, mix)
     else:
         sigma, rho = smooth_knn_dist(dist, float(k), local_connectivity=lc)
-        self_rows = torch.arange(N, device=X.device)
+        self_rows = torch.arange(N, device=dev)
         w = membership_strengths(idx, dist, sigma, rho, self_rows)
         rows = self_rows.view(-1, 1).expand_as(idx).reshape(-1)
         cols = idx.reshape(-1)
         rows, cols, vals = fuzzy_union(rows, cols.clamp_min(0), w.reshape(-1), N, mix)
     if y is not None:
-        yy = y.to(X.device).long().view(-1)
+        yy = y.to(dev).long().view(-1)
         if order is not None:
             yy = yy[order]
         rows, cols, vals = categorical_intersection(rows, cols, vals, yy, N)
@@ -639,13 +672,13 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
     init = params.get("init", "spectral")
     from .knn_graph import record_phase
 
-    record_phase(phases, "fuzzy_union", N, t_ph, X.device)
+    record_phase(phases, "fuzzy_union", N, t_ph, dev)
     # every rank computes the same initial layout (the spectral iteration row-partitioned)
     if isinstance(init, str) and init == "spectral" and N > dim + 1:
         emb = spectral_init(rows, cols, vals, N, dim, seed, ctx=dist_ctx, phases=phases)
     else:
-        g = torch.Generator(device=X.device).manual_seed(seed)
-        emb = torch.rand((N, dim), generator=g, device=X.device) * 20.0 - 10.0
+        g = torch.Generator(device=dev).manual_seed(seed)
+        emb = torch.rand((N, dim), generator=g, device=dev) * 20.0 - 10.0
     mn, mx = emb.min(0).values, emb.max(0).values
     emb = (10.0 * (emb - mn) / (mx - mn).clamp_min(1e-30)).float().contiguous()
     if dist_ctx is not None and dist_ctx.world_size > 1:
@@ -656,7 +689,7 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
     optimize_layout(emb, emb, rows, cols, vals, n_epochs, a, b, float(params.get("repulsion_strength", 1.0)),
                     float(params.get("learning_rate", 1.0)), float(params.get("negative_sample_rate", 5)), True, seed,
                     ctx=dist_ctx, pull=PULL, phases=phases)
-    record_phase(phases, "epochs", phases.get("epochs", {}).get("rows", 0), t_ep, X.device)
+    record_phase(phases, "epochs", phases.get("epochs", {}).get("rows", 0), t_ep, dev)
     LAST_PHASES.update(phases)
     if order is not None:
         out = torch.empty_like(emb)
@@ -665,7 +698,14 @@ def umap_fit(X: torch.Tensor, params: Dict[str, Any], y: Optional[torch.Tensor] 
     return emb.cpu().numpy()
 
 
-def umap_transform(X: torch.Tensor, raw: torch.Tensor, embedding: torch.Tensor, params: Dict[str, Any]) -> np.ndarray:
+def umap_transform(X: Any, raw: Any, embedding: torch.Tensor, params: Dict[str, Any]) -> np.ndarray:
+    """Embedding of new rows ``X`` next to the training rows ``raw``: both dense tensors, or both
+    device ``CSR`` (a sparse-fitted model; its caller converts dense partitions to CSR)."""
+    from .knn_graph import is_csr, knn_graph_csr
+
+    if is_csr(X) != is_csr(raw):
+        raise TypeError("umap_transform: new rows and training rows must both be dense or both be CSR")
+    dev = X.device
     Nn = X.shape[0]
     Ntr = raw.shape[0]
     k = int(min(params.get("n_neighbors", 15), Ntr))
@@ -676,16 +716,20 @@ def umap_transform(X: torch.Tensor, raw: torch.Tensor, embedding: torch.Tensor, 
     if a is None or b is None:
         a, b = find_ab_params(float(params.get("spread", 1.0)), float(params.get("min_dist", 0.1)))
     kind, pre_map, post_map, mink_p = resolve_metric(metric, params.get("metric_kwds"))
-    Xf, Rf = _metric_rows(X.float().contiguous(), pre_map), _metric_rows(raw.float().contiguous(), pre_map)
-    if kind == "euclidean":
-        dist, idx = knn_graph(Xf, Rf, k)
+    if is_csr(raw):
+        Xf, Rf = _sparse_metric_rows(X, metric, kind, pre_map), _sparse_metric_rows(raw, metric, kind, pre_map)
+        dist, idx = knn_graph_csr(Xf, Rf, k, kind)
     else:
-        from .knn_graph import knn_graph_metric
+        Xf, Rf = _metric_rows(X.float().contiguous(), pre_map), _metric_rows(raw.float().contiguous(), pre_map)
+        if kind == "euclidean":
+            dist, idx = knn_graph(Xf, Rf, k)
+        else:
+            from .knn_graph import knn_graph_metric
 
-        dist, idx = knn_graph_metric(Xf, Rf, k, kind, mink_p)
+            dist, idx = knn_graph_metric(Xf, Rf, k, kind, mink_p)
     dist = _metric_dist(dist, post_map)
     adj_lc = max(0.0, float(params.get("local_connectivity", 1.0)) - 1.0)
-    if X.is_cuda:
+    if dev.type == "cuda":
         _, _, w = ops.umap_smooth_knn(dist, idx, float(k), local_connectivity=adj_lc, self_rows=False)
     else:
         sigma, rho = smooth_knn_dist(dist, float(k), local_connectivity=adj_lc)
@@ -697,7 +741,7 @@ def umap_transform(X: torch.Tensor, raw: torch.Tensor, embedding: torch.Tensor, 
     n_epochs = int(n_epochs) // 3 if n_epochs else (100 if Nn <= 10000 else 30)
     if n_epochs <= 0:
         return init.cpu().numpy()
-    rows = torch.arange(Nn, device=X.device).view(-1, 1).expand_as(idx).reshape(-1)
+    rows = torch.arange(Nn, device=dev).view(-1, 1).expand_as(idx).reshape(-1)
     cols = idx.reshape(-1).clamp_min(0)
     vals = w.reshape(-1)
     emb = optimize_layout(init, emb_tr.clone(), rows, cols, vals, n_epochs, a, b,

@@ -3501,6 +3501,276 @@ def csr_col_moments(A) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 # ------------------------------------------------------------------------------------------
+# Exact nearest neighbours between two CSR row sets (csrc/csr_knn.hip): UMAP on sparse features
+CSR_KNN_CODES = {"sqeuclidean": 0, "hellinger": 1, "jaccard": 2}  # metric codes of srml_csr_pairdist_f32
+CSR_KNN_ALIASES = {"euclidean": "sqeuclidean", "l2": "sqeuclidean", "sqeuclidean": "sqeuclidean",
+                   "hellinger": "hellinger", "jaccard": "jaccard"}
+# dispatch constants of csrc/csr_knn.hip (srml_csr_knn_config returns the same five)
+CSR_KNN_W = 1024            # columns per LDS window (CK_W)
+CSR_KNN_TQ = 16             # query rows per block (CK_TQ)
+CSR_KNN_TI = 512            # item rows per block, one per thread (CK_TI)
+CSR_KNN_COOP = 64           # non-zeros of one (row, window) from which the wave shares the row (CK_COOP)
+CSR_REFINE_LDS_CAP = 2048   # query non-zeros the refine kernel stages in LDS (RF_CAP)
+
+
+class CSRRows:
+    """Rows of a CSR matrix as the sparse kNN kernels read them (``csr_prepare``): the values the
+    metric's key is computed from, the per-row auxiliary (squared norms / non-zero counts / None)
+    and ABSOLUTE row offsets — ``rows(lo, hi)`` is a view of a row block whose ``indptr`` still
+    indexes the whole ``indices`` / ``data`` arrays."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, shape: Tuple[int, int],
+                 aux: Optional[torch.Tensor], metric: str) -> None:
+        self.indptr, self.indices, self.data, self.shape, self.aux, self.metric = (indptr, indices, data,
+                                                                                    (int(shape[0]), int(shape[1])), aux,
+                                                                                    metric)
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def rows(self, lo: int, hi: int) -> "CSRRows":
+        lo, hi = max(0, int(lo)), min(self.shape[0], int(hi))
+        return CSRRows(self.indptr[lo: hi + 1], self.indices, self.data, (max(0, hi - lo), self.shape[1]),
+                       None if self.aux is None else self.aux[lo:hi], self.metric)
+
+    def to_dense(self, lo: int = 0, hi: Optional[int] = None) -> torch.Tensor:
+        """Rows lo .. hi as a dense matrix of the prepared values."""
+        hi = self.shape[0] if hi is None else min(int(hi), self.shape[0])
+        ip = self.indptr[lo: hi + 1]
+        a, b = int(ip[0]), int(ip[-1])
+        out = zeros((hi - lo, self.shape[1]), dtype=self.data.dtype, device=self.data.device)
+        rows = torch.repeat_interleave(torch.arange(hi - lo, device=ip.device), ip[1:] - ip[:-1])
+        out[rows, self.indices[a:b].long()] = self.data[a:b]
+        return out
+
+
+def csr_knn_metric(metric: str) -> str:
+    name = CSR_KNN_ALIASES.get(str(metric).lower())
+    if name is None:
+        raise ValueError("Unsupported sparse kNN metric %r (%s)" % (metric, ", ".join(sorted(CSR_KNN_ALIASES))))
+    return name
+
+
+def _csr_block_row_sums(indptr: torch.Tensor, vals: torch.Tensor, m: int) -> torch.Tensor:
+    """fp64 sums of vals[indptr[r] : indptr[r + 1]] for r < m (absolute offsets; one thread per row on
+    the device, a fixed order either way)."""
+    if vals.is_cuda and vals.dtype == torch.float32:
+        out = torch.empty(m, dtype=torch.float64, device=vals.device)
+        native.call("srml_csr_row_sums_f32", _c(indptr).data_ptr(), vals.data_ptr(), m, out.data_ptr(),
+                    native.stream(vals.device))
+        return out
+    a = int(indptr[0]) if m else 0
+    rows = torch.repeat_interleave(torch.arange(m, device=vals.device), indptr[1:] - indptr[:-1])
+    return zeros(m, dtype=torch.float64, device=vals.device).index_add_(0, rows, vals[a: a + rows.numel()].double())
+
+
+def csr_prepare(A: Any, metric: str) -> CSRRows:
+    """The rows of the CSR ``A`` (indptr int64, indices int32, data, shape; ``indptr`` may be a
+    slice of a larger matrix's row offsets) prepared for ``metric``:
+
+    * ``sqeuclidean`` (``euclidean``, ``l2``): the values, aux = row squared norms (fp32 of an fp64 sum);
+    * ``hellinger``: the square roots of the values (negative input raises), no aux;
+    * ``jaccard``: indicator values (1 where the stored value is non-zero), aux = non-zero counts.
+
+    Checked once, with ``ValueError`` otherwise: row offsets monotone inside the arrays, every
+    column index in [0, n), indices strictly increasing within each row. The kernels' LDS scatter
+    and binary searches depend on it and do not check again."""
+    name = csr_knn_metric(metric)
+    if isinstance(A, CSRRows):
+        if A.metric != name:
+            raise ValueError("CSR rows were prepared for %r, not %r" % (A.metric, name))
+        return A
+    m, n = int(A.shape[0]), int(A.shape[1])
+    indptr, indices, data = A.indptr, A.indices, A.data
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise TypeError("CSR kernels need int64 row offsets and int32 column indices")
+    if indptr.numel() != m + 1 or indices.numel() != data.numel():
+        raise ValueError("inconsistent CSR arrays")
+    if not data.is_floating_point():
+        data = data.float()
+    a, b = (int(indptr[0]), int(indptr[-1])) if m else (0, 0)
+    if a < 0 or b > indices.numel() or b < a or bool((indptr[1:] < indptr[:-1]).any()):
+        raise ValueError("CSR row offsets are not a monotone sequence inside the index array")
+    idx = indices[a:b]
+    if idx.numel():
+        if bool(((idx < 0) | (idx >= n)).any()):
+            raise ValueError("CSR column index out of range [0, %d)" % n)
+        rising = idx[1:] > idx[:-1]
+        starts = indptr[1:-1] - a  # first non-zero of rows 1 .. m - 1; equal to a neighbour's for empty rows
+        starts = starts[(starts > 0) & (starts < idx.numel())]
+        rising[starts - 1] = True  # a row's first index follows another row's last: no order between them
+        if not bool(rising.all()):
+            raise ValueError("CSR column indices must be strictly increasing within each row")
+    vals = data[a:b]
+    aux = None
+    if name == "hellinger":
+        if vals.numel() and bool((vals < 0).any()):
+            raise ValueError("hellinger distance needs non-negative input")
+        vals = torch.sqrt(vals)
+    elif name == "jaccard":
+        vals = (vals != 0).to(data.dtype)
+    if a == 0 and b == data.numel():
+        data = vals
+    else:  # a row block: the values outside it are never read
+        full = zeros(data.numel(), dtype=data.dtype, device=data.device)
+        full[a:b] = vals
+        data = full
+    data = _c(data)
+    if name == "sqeuclidean":
+        aux = _csr_block_row_sums(indptr, data * data, m).float()
+    elif name == "jaccard":
+        aux = _csr_block_row_sums(indptr, data, m).float()
+    return CSRRows(indptr, _c(indices), data, (m, n), aux, name)
+
+
+def _csr_native(Q: CSRRows, I: CSRRows) -> bool:
+    return Q.data.is_cuda and I.data.is_cuda and Q.data.dtype == torch.float32 and I.data.dtype == torch.float32
+
+
+def _csr_pairdist_launch(Q: CSRRows, q0: int, r: int, I: CSRRows, i0: int, L: int, D: torch.Tensor) -> None:
+    """D[:r, :L] = key(Q rows q0 .. q0 + r, I rows i0 .. i0 + L): one launch of ``srml_csr_pairdist_f32``."""
+    qip, iip = _c(Q.indptr), _c(I.indptr)
+    qa = Q.aux[q0:].data_ptr() if Q.aux is not None else None
+    ia = I.aux[i0:].data_ptr() if I.aux is not None else None
+    rc = native.call_status("srml_csr_pairdist_f32", qip[q0:].data_ptr(), Q.indices.data_ptr(), Q.data.data_ptr(), qa,
+                            r, iip[i0:].data_ptr(), I.indices.data_ptr(), I.data.data_ptr(), ia, L, Q.shape[1],
+                            CSR_KNN_CODES[Q.metric], D.data_ptr(), D.stride(0), native.stream(D.device))
+    if rc < 0:
+        raise ValueError("srml_csr_pairdist_f32 refused the launch (status %d: -1 grid overflow, -2 metric / n, -9 LDS)"
+                         % rc)
+    if rc != 0:
+        raise RuntimeError("srml_csr_pairdist_f32 launch failed with HIP status %d" % rc)
+
+
+def _csr_keys_torch(Q: CSRRows, q0: int, r: int, I: CSRRows, i0: int, L: int) -> torch.Tensor:
+    """The kernel's keys as torch expressions on densified row chunks (CPU CI path, fp64 data)."""
+    q, it = Q.to_dense(q0, q0 + r), I.to_dense(i0, i0 + L).to(Q.data.dtype)
+    if Q.metric == "sqeuclidean":
+        d = Q.aux[q0: q0 + r].to(q.dtype).view(-1, 1) + I.aux[i0: i0 + L].to(q.dtype).view(1, -1) - 2.0 * (q @ it.T)
+        return d.clamp_min(0)
+    return _pairdist_expr(q, it, Q.metric, 2.0)
+
+
+def _csr_pair(Q: Any, I: Any, metric: str) -> Tuple[CSRRows, CSRRows]:
+    Qp = csr_prepare(Q, metric)
+    Ip = Qp if I is Q else csr_prepare(I, metric)
+    if Qp.shape[1] != Ip.shape[1]:
+        raise ValueError("sparse kNN: %d vs %d features" % (Qp.shape[1], Ip.shape[1]))
+    return Qp, Ip
+
+
+def _csr_torch_rows(n: int, esize: int) -> int:
+    """Rows of a densified chunk within the torch form's byte budget."""
+    return max(1, min(4096, _PAIRDIST_CPU_BYTES // max(1, n * esize)))
+
+
+def csr_pairwise_dist(Q: Any, I: Any, metric: str) -> torch.Tensor:
+    """The full key matrix D[q, i] of two CSR row sets (tests and small inputs): squared Euclidean
+    distances in expanded form, Hellinger or Jaccard distances (``csr_prepare``'s table). fp32
+    device CSRs: ``srml_csr_pairdist_f32``; otherwise densified row chunks through torch."""
+    Qp, Ip = _csr_pair(Q, I, metric)
+    mq, mi = Qp.shape[0], Ip.shape[0]
+    D = torch.empty((mq, mi), dtype=torch.float32, device=Qp.device)
+    if not D.numel():
+        return D
+    if _csr_native(Qp, Ip) and Qp.shape[1] > 0:
+        _csr_pairdist_launch(Qp, 0, mq, Ip, 0, mi, D)
+        return D
+    step = _csr_torch_rows(Qp.shape[1], Qp.data.element_size())
+    for q0 in range(0, mq, step):
+        for i0 in range(0, mi, step):
+            r, L = min(step, mq - q0), min(step, mi - i0)
+            D[q0: q0 + r, i0: i0 + L] = _csr_keys_torch(Qp, q0, r, Ip, i0, L).float()
+    return D
+
+
+def csr_knn(Q: Any, I: Any, k: int, metric: str, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact k nearest rows of the CSR ``I`` for every row of the CSR ``Q``: (keys fp32 [mq, k]
+    ascending, ids int64 [mq, k]); ties go to the lower id, k > mi pads +inf / -1. The keys are
+    ``csr_pairwise_dist``'s: squared Euclidean ones come from the expanded form and only SELECT
+    (``csr_refine_sort`` gives the distances); Hellinger and Jaccard keys are sums without
+    cancellation. Per (query chunk, item chunk) the keys are materialised in one reused buffer of at
+    most ``_KNN_DIST_BYTES`` and selected by ``topk_rows``, which also merges the chunks, as
+    ``knn_metric`` does. Either operand may be a ``csr_prepare`` result (or a ``rows`` block of one)."""
+    Qp, Ip = _csr_pair(Q, I, metric)
+    mq, mi = Qp.shape[0], Ip.shape[0]
+    if k < 1 or k > TOPK_KMAX:
+        raise ValueError("csr_knn: k=%d outside [1, %d]" % (k, TOPK_KMAX))
+    dev = Qp.device
+    if mq == 0 or mi == 0:
+        return (torch.full((mq, k), float("inf"), dtype=torch.float32, device=dev),
+                torch.full((mq, k), -1, dtype=torch.int64, device=dev))
+    if not (_csr_native(Qp, Ip) and Qp.shape[1] > 0):
+        step = _csr_torch_rows(Qp.shape[1], Qp.data.element_size())
+        outs = []
+        for q0 in range(0, mq, step):
+            r = min(step, mq - q0)
+            parts = [topk_rows(_csr_keys_torch(Qp, q0, r, Ip, i0, min(step, mi - i0)).float(), k,
+                               id_base=i0 + int(id_offset)) for i0 in range(0, mi, step)]
+            outs.append(parts[0] if len(parts) == 1 else
+                        topk_rows(torch.cat([v for v, _ in parts], 1), k, ids=torch.cat([i for _, i in parts], 1)))
+        return torch.cat([v for v, _ in outs]), torch.cat([i for _, i in outs])
+    Lc = min(mi, 16 * _TOPK_SLICE, max(CSR_KNN_TI, (_KNN_DIST_BYTES // (4 * CSR_KNN_TQ)) // CSR_KNN_TI * CSR_KNN_TI))
+    R = max(CSR_KNN_TQ, min(4096, (_KNN_DIST_BYTES // (Lc * 4)) // CSR_KNN_TQ * CSR_KNN_TQ))
+    nchunks = (mi + Lc - 1) // Lc
+    outv = torch.empty((mq, k), dtype=torch.float32, device=dev)
+    outi = torch.empty((mq, k), dtype=torch.int64, device=dev)
+    D = torch.empty((min(R, mq), Lc), dtype=torch.float32, device=dev)
+    for q0 in range(0, mq, R):
+        r = min(R, mq - q0)
+        parts_v, parts_i = [], []
+        for c in range(nchunks):
+            i0 = c * Lc
+            L = min(Lc, mi - i0)
+            _csr_pairdist_launch(Qp, q0, r, Ip, i0, L, D)
+            v, i = topk_rows(D[:r, :L], k, id_base=i0 + int(id_offset))
+            parts_v.append(v)
+            parts_i.append(i)
+        if nchunks > 1:
+            v, i = topk_rows(torch.cat(parts_v, 1), k, ids=torch.cat(parts_i, 1))
+        else:
+            v, i = parts_v[0], parts_i[0]
+        outv[q0: q0 + r] = v
+        outi[q0: q0 + r] = i
+    return outv, outi
+
+
+def csr_refine_sort(Q: Any, I: Any, ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Squared Euclidean distances of each query row's candidate rows ``ids`` (int64 [mq, k], row
+    numbers of ``I``, -1 = none) in DIRECT form — every (x_j - y_j)^2 over the union of the two
+    supports is computed as such and summed, no difference of sums — sorted ascending per row (ties
+    keep the candidate order, missing candidates last at +inf): (d2 fp32, ids int64). The CSR twin
+    of ``knn_refine_sort``: ``srml_csr_refine_f32`` (one wave per pair) for fp32 device CSRs, gathered
+    dense row chunks through torch otherwise."""
+    Qp, Ip = _csr_pair(Q, I, "sqeuclidean")
+    mq, k = ids.shape
+    ids = _c(ids.to(torch.int64))
+    d = torch.empty((mq, k), dtype=torch.float32, device=Qp.device)
+    if mq and k and _csr_native(Qp, Ip):
+        native.call("srml_csr_refine_f32", _c(Qp.indptr).data_ptr(), Qp.indices.data_ptr(), Qp.data.data_ptr(), mq,
+                    _c(Ip.indptr).data_ptr(), Ip.indices.data_ptr(), Ip.data.data_ptr(), Ip.shape[0], ids.data_ptr(), k,
+                    ids.stride(0), d.data_ptr(), d.stride(0), native.stream(d.device))
+    elif mq and k:
+        n = Qp.shape[1]
+        step = max(1, (_PAIRDIST_CPU_BYTES // 4) // max(1, (k + 1) * n * Qp.data.element_size()))
+        for s in range(0, mq, step):
+            e = min(mq, s + step)
+            sel = ids[s:e].clamp(0, max(0, Ip.shape[0] - 1)).reshape(-1)
+            lo, hi = int(sel.min()), int(sel.max()) + 1
+            if (hi - lo) * n * Ip.data.element_size() <= _PAIRDIST_CPU_BYTES:
+                rows, inv = Ip.to_dense(lo, hi), sel - lo
+            else:  # candidates far apart: densify them one by one
+                uniq, inv = torch.unique(sel, return_inverse=True)
+                rows = torch.stack([Ip.to_dense(u, u + 1)[0] for u in uniq.tolist()])
+            diff = rows.to(Qp.data.dtype)[inv].view(e - s, k, n) - Qp.to_dense(s, e).unsqueeze(1)
+            d[s:e] = (diff * diff).sum(-1).float()
+    d = torch.where((ids >= 0) & (ids < Ip.shape[0]), d, torch.full_like(d, float("inf")))
+    d, j = torch.sort(d, dim=1, stable=True)
+    return d, ids.gather(1, j)
+
+
+# ------------------------------------------------------------------------------------------
 # Logistic loss + gradient accumulation for the on-device quasi-Newton driver (models/qn.py)
 def _is_csr(X) -> bool:
     return hasattr(X, "indptr") and hasattr(X, "indices")

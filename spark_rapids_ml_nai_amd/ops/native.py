@@ -208,6 +208,10 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_csr_spmtm_ld_f32": (_P, _P, _P, _L, _L, _P, _I, _L, _P, _L, _P),
     "srml_csr_spmtm_ld_f64": (_P, _P, _P, _L, _L, _P, _I, _L, _P, _L, _P),
     "srml_csr_row_sums_f32": (_P, _P, _L, _P, _P),
+    # CSR x CSR nearest neighbours: (row offsets, indices, values, aux, rows) per operand, n, metric, D, ldd
+    "srml_csr_knn_config": (_I,),
+    "srml_csr_pairdist_f32": (_P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _I, _I, _P, _L, _P),
+    "srml_csr_refine_f32": (_P, _P, _P, _L, _P, _P, _P, _L, _P, _I, _L, _P, _L, _P),
     "srml_confusion_counts": (_P, _I, _P, _I, _L, _I, _P, _P),
     "srml_logloss_sum": (_P, _I, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_reg_moments": (_P, _I, _P, _I, _L, _P, _P),

@@ -12,6 +12,13 @@ minkowski (``metric_kwds={"p": ...}``), canberra, hamming, jaccard and hellinger
 distance kernel (exact graph only, O(N^2)) — ``init`` spectral or
 random, supervised fits through ``labelCol`` (categorical target intersection), ``a``/``b``
 overrides, ``precomputed_knn`` (indices, distances), ``random_state``.
+
+Sparse features (``enable_sparse_data_optim=True``, or ``None`` and a first row that is a
+``SparseVector``): the rows stay CSR from the vector column to the device, the kNN graph comes from
+the exact CSR search (``models.knn_graph.knn_graph_csr``; euclidean / l2 / sqeuclidean / cosine /
+hellinger / jaccard) and the model keeps ``raw_data_`` as a ``scipy.sparse.csr_matrix``. The default
+is ``False`` (densify, as before): a densified fit above 100k rows uses the approximate IVF builder,
+the CSR search is exact and O(N^2) at every size.
 """
 from __future__ import annotations
 
@@ -23,6 +30,7 @@ import torch
 from .core.base import _dense_from_df, _Estimator, _Model, run_worker_job
 from .core.dataframe import DataFrame, as_dataframe
 from .core.params import (
+    HasEnableSparseDataOptim,
     HasFeaturesCol,
     HasFeaturesCols,
     HasLabelCol,
@@ -62,7 +70,8 @@ def _p(name: str, doc: str, conv: Callable) -> Param:
     return Param(Params._dummy(), name, doc, typeConverter=conv)
 
 
-class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol):
+class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasOutputCol,
+                  HasEnableSparseDataOptim):
     n_neighbors = _p("n_neighbors", "The size of local neighborhood used for manifold approximation.",
                      TypeConverters.toFloat)
     n_components = _p("n_components", "The dimension of the space to embed into.", TypeConverters.toInt)
@@ -107,6 +116,9 @@ class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatures
                          repulsion_strength=1.0, negative_sample_rate=5, transform_queue_size=4.0, a=None, b=None,
                          precomputed_knn=None, random_state=None, sample_fraction=1.0, outputCol="embedding",
                          featuresCol="features", build_algo="auto", build_kwds=None)
+        # the shared Param's default is None (the first row decides); UMAP keeps every existing call
+        # on the dense route until a sparse approximate graph builder exists
+        self._setDefault(enable_sparse_data_optim=False)
 
     def getSampleFraction(self) -> float:
         return self.getOrDefault(self.sample_fraction)
@@ -143,18 +155,61 @@ for _n in _UMAP_KEYS:
         setattr(_UMAPParams, "set" + _cap[0].upper() + _cap[1:], lambda self, v, _k=_n: self._set_params(**{_k: v}))
 
 
-def _umap_fit_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarray, np.ndarray]:
+def _host_csr(X: Any) -> Any:
+    """fp32 ``scipy.sparse.csr_matrix`` with sorted, duplicate-free indices and int64 / int32 index arrays
+    (what the CSR kernels read); the caller's matrix is left as it is."""
+    import scipy.sparse as sp
+
+    A = sp.csr_matrix(X, dtype=np.float32)
+    if not A.has_canonical_format:
+        A = A.copy()
+        A.sum_duplicates()  # sorts the indices too
+    return A
+
+
+def allgather_csr(A: Any, comm: Any) -> Any:
+    """The row-wise concatenation of every rank's device ``CSR`` piece, on every rank: values, column
+    indices and per-row non-zero counts are ``allgatherv``-ed and the row offsets rebuilt by a cumulative
+    sum (a piece may be empty; the width is the widest piece's)."""
+    from .core.base import CSR
+
+    dev = A.data.device
+    counts = (A.indptr[1:] - A.indptr[:-1]).contiguous()
+    vals = torch.cat([p.to(dev) for p in comm.allgatherv(A.data.contiguous())])
+    idx = torch.cat([p.to(dev) for p in comm.allgatherv(A.indices.contiguous())])
+    cnt = torch.cat([p.to(dev) for p in comm.allgatherv(counts)])
+    width = torch.cat([p.to(dev) for p in comm.allgatherv(torch.tensor([int(A.shape[1])], dtype=torch.int64,
+                                                                       device=dev))])
+    indptr = torch.zeros(cnt.numel() + 1, dtype=torch.int64, device=dev)
+    indptr[1:] = torch.cumsum(cnt, 0)
+    return CSR(indptr=indptr, indices=idx.to(torch.int32), data=vals, shape=(int(cnt.numel()), int(width.max())))
+
+
+def _csr_to_host(A: Any) -> Any:
+    import scipy.sparse as sp
+
+    return sp.csr_matrix((A.data.cpu().numpy(), A.indices.cpu().numpy(), A.indptr.cpu().numpy()),
+                         shape=tuple(A.shape))
+
+
+def _umap_fit_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarray, Any]:
+    import scipy.sparse as sp
+
     from .core.base import to_device
     from .models.umap import umap_fit
 
     X, y, params = payload[:3]
     every_rank = len(payload) > 3 and bool(payload[3])
-    Xh = np.ascontiguousarray(X, dtype=np.float32)
-    Xd = to_device(Xh, ctx.device, torch.float32)
+    sparse = sp.issparse(X)
+    Xh = _host_csr(X) if sparse else np.ascontiguousarray(X, dtype=np.float32)
+    Xd = to_device(Xh, ctx.device, torch.float32)  # a scipy CSR arrives as a device ``CSR``
     yd = torch.as_tensor(np.asarray(y), device=ctx.device) if y is not None else None
     if ctx.world_size > 1:
         # every rank holds the whole (sampled) training set: device all-gather over RCCL
-        Xd = torch.cat([p.to(ctx.device) for p in ctx.comm.allgatherv(Xd)], 0)
+        if sparse:
+            Xd = allgather_csr(Xd, ctx.comm)
+        else:
+            Xd = torch.cat([p.to(ctx.device) for p in ctx.comm.allgatherv(Xd)], 0)
         if yd is not None:
             yd = torch.cat([p.to(ctx.device) for p in ctx.comm.allgatherv(yd)], 0)
     emb = umap_fit(Xd, params, yd, ctx=ctx)
@@ -164,6 +219,8 @@ def _umap_fit_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.n
         return None, None
     # the model's raw_data_: one rank already holds all rows on the host (no 4 B x N x n copy back
     # from the device: ~0.5 s at 20M x 128); several ranks return the device-gathered rows
+    if sparse:
+        return emb, (Xh if ctx.world_size == 1 else _csr_to_host(Xd))
     return emb, (Xh if ctx.world_size == 1 else Xd.cpu().numpy())
 
 
@@ -266,7 +323,8 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
                  transform_queue_size: Optional[float] = 4.0, a: Optional[float] = None, b: Optional[float] = None,
                  precomputed_knn: Optional[Any] = None, random_state: Optional[int] = None,
                  sample_fraction: Optional[float] = 1.0, featuresCol: Optional[Union[str, List[str]]] = None,
-                 labelCol: Optional[str] = None, outputCol: Optional[str] = None, num_workers: Optional[int] = None,
+                 labelCol: Optional[str] = None, outputCol: Optional[str] = None,
+                 enable_sparse_data_optim: Optional[bool] = False, num_workers: Optional[int] = None,
                  verbose: Union[int, bool] = False, **kwargs: Any) -> None:
         super().__init__()
         self._set_params(**self._input_kwargs)
@@ -279,6 +337,48 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
 
     def _create_model(self, result: Dict[str, Any]) -> "UMAPModel":
         return UMAPModel._from_row(result)
+
+    def _supports_sparse(self) -> bool:
+        return True
+
+    def _sparse_route(self, df: DataFrame) -> bool:
+        """Whether this fit keeps the features CSR: decided once for the whole frame (``True`` / the
+        first row for ``None`` / ``False``, the shared Param's meaning); the metric is checked here,
+        before any worker starts."""
+        fc = self.getFeaturesCol()
+        if not isinstance(fc, str) or not self._use_sparse(df, fc):
+            return False
+        from .models.umap import check_sparse_metric, resolve_metric
+
+        metric = self._backend_params.get("metric", "euclidean")
+        kind, pre, _, _ = resolve_metric(metric, self._backend_params.get("metric_kwds"))
+        check_sparse_metric(metric, kind, pre)
+        return True
+
+    def _features(self, df: DataFrame, sparse: bool = False) -> Any:
+        if sparse:
+            from .core.dataframe import vector_column_to_csr
+
+            return vector_column_to_csr(df.column(self.getFeaturesCol()), np.float32)
+        return super()._features(df)
+
+    def _refuse_sparse_spark(self, sdf: Any) -> None:
+        """A sparse route on a pyspark frame: refused before any job starts (the barrier fit streams
+        ``raw_data_`` back as float lists; carrying a CSR through it is not implemented)."""
+        if self.getOrDefault("enable_sparse_data_optim") is not True:
+            return  # None would need a job to read the first row: pyspark frames take the dense route
+        fc = self.getFeaturesCol()
+        if not isinstance(fc, str):
+            return
+        try:
+            is_vector = type(sdf.schema[fc].dataType).__name__ == "VectorUDT"
+        except Exception:  # noqa: BLE001
+            is_vector = True  # the column type is unknown: refuse instead of starting a job
+        if is_vector:
+            raise NotImplementedError(
+                "UMAP(enable_sparse_data_optim=True) on a pyspark DataFrame is not implemented: the Spark barrier fit "
+                "returns raw_data_ as dense float lists. Fit an in-process DataFrame / pandas frame (num_workers > 1 "
+                "and SPMD are supported), or set enable_sparse_data_optim=False.")
 
     def _spark_fit(self, sdf: Any) -> Tuple[np.ndarray, np.ndarray]:
         from .parallel.spark import spark_barrier_job
@@ -313,6 +413,7 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
 
         self._check_metric()
         if is_spark_dataframe(dataset):
+            self._refuse_sparse_spark(dataset)
             emb, Xall = self._spark_fit(dataset)
             return self._make_model(emb, Xall)
         df, _ = as_dataframe(dataset)
@@ -329,8 +430,9 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
         from .core.base import spmd_active
 
         nw = self.num_workers
+        sparse = self._sparse_route(df)
         if spmd_active() or nw <= 1:
-            payloads = [(self._features(df), y, params, spmd_active())]
+            payloads = [(self._features(df, sparse), y, params, spmd_active())]
         else:
             if df.getNumPartitions() != nw:
                 df = df.repartition(nw)
@@ -338,11 +440,11 @@ class UMAP(UMAPClass, _Estimator, _UMAPParams):
             for p in df.partitions:
                 part = DataFrame([p])
                 yp = part.to_numpy(self.getLabelCol()).astype(np.int64) if y is not None else None
-                payloads.append((self._features(part), yp, params))
+                payloads.append((self._features(part, sparse), yp, params))
         emb, Xall = run_worker_job(_umap_fit_worker, payloads)[0]
         return self._make_model(emb, Xall)
 
-    def _make_model(self, emb: np.ndarray, Xall: np.ndarray) -> "UMAPModel":
+    def _make_model(self, emb: np.ndarray, Xall: Any) -> "UMAPModel":
         model = UMAPModel(embedding_=emb, raw_data_=Xall, n_cols=int(Xall.shape[1]), dtype="float32")
         model.BROADCAST_LIMIT = int(self.BROADCAST_LIMIT)
         model._num_workers = self._num_workers
@@ -356,13 +458,48 @@ class UMAPModel(UMAPClass, _Model, _UMAPParams):
     BROADCAST_LIMIT = 8 << 30
 
     def __init__(self, embedding_: Any, raw_data_: Any, n_cols: int, dtype: str) -> None:
+        import scipy.sparse as sp
+
         emb = np.asarray(embedding_, dtype=np.float32)
-        raw = np.asarray(raw_data_, dtype=np.float32)
+        # a sparse fit keeps its training rows CSR (fp32); a dense fit an N x n array, as before
+        raw = _host_csr(raw_data_) if sp.issparse(raw_data_) else np.asarray(raw_data_, dtype=np.float32)
         super().__init__(embedding_=emb, raw_data_=raw, n_cols=n_cols, dtype=dtype)
         self.embedding_ = emb
         self.raw_data_ = raw
         self.n_cols = int(n_cols)
         self.dtype = dtype
+
+    def _sparse_fitted(self) -> bool:
+        import scipy.sparse as sp
+
+        return sp.issparse(self.raw_data_)
+
+    def _transform_supports_sparse(self) -> bool:
+        return self._sparse_fitted()
+
+    def _get_model_attributes(self) -> Dict[str, Any]:
+        """What persistence writes. A sparse ``raw_data_`` goes out as its three arrays plus a flag
+        (each array a ``.npy`` side file above 65 536 elements, JSON below: the writer's rule); a dense
+        model's attributes are unchanged."""
+        if not self._sparse_fitted():
+            return self._model_attributes
+        raw = self.raw_data_
+        return {"embedding_": self.embedding_, "raw_data_sparse": True,
+                "raw_data_indptr": np.asarray(raw.indptr, dtype=np.int64),
+                "raw_data_indices": np.asarray(raw.indices, dtype=np.int32),
+                "raw_data_values": np.asarray(raw.data, dtype=np.float32), "n_cols": self.n_cols, "dtype": self.dtype}
+
+    @classmethod
+    def _from_row(cls, model_attributes: Any) -> "UMAPModel":
+        d = model_attributes.asDict() if hasattr(model_attributes, "asDict") else dict(model_attributes)
+        if d.pop("raw_data_sparse", False):
+            import scipy.sparse as sp
+
+            indptr = np.asarray(d.pop("raw_data_indptr"), dtype=np.int64)
+            d["raw_data_"] = sp.csr_matrix((np.asarray(d.pop("raw_data_values"), dtype=np.float32),
+                                            np.asarray(d.pop("raw_data_indices"), dtype=np.int32), indptr),
+                                           shape=(indptr.shape[0] - 1, int(d["n_cols"])))
+        return cls(**d)
 
     @property
     def embedding(self) -> List[List[float]]:
@@ -370,6 +507,10 @@ class UMAPModel(UMAPClass, _Model, _UMAPParams):
 
     @property
     def raw_data(self) -> List[List[float]]:
+        """The training rows as nested lists. A sparse-fitted model DENSIFIES its CSR ``raw_data_`` here
+        (N x n_cols floats): read ``raw_data_`` itself to keep it sparse."""
+        if self._sparse_fitted():
+            return self.raw_data_.toarray().tolist()
         return self.raw_data_.tolist()
 
     def _spark_task_model(self, spark: Any) -> "UMAPModel":
@@ -402,16 +543,31 @@ class UMAPModel(UMAPClass, _Model, _UMAPParams):
         src = getattr(self, "_sources", None)
         emb, raw = (self.embedding_, self.raw_data_) if src is None else src
 
-        def construct(ctx: WorkerContext) -> Tuple[torch.Tensor, torch.Tensor]:
+        sparse = self._sparse_fitted()
+
+        def construct(ctx: WorkerContext) -> Tuple[Any, torch.Tensor]:
+            from .core.base import to_device
+
             e, r = (emb, raw) if src is None else (emb.value(), raw.value())
+            if sparse:  # the training rows go to the device as a CSR
+                return to_device(r, ctx.device, torch.float32), torch.from_numpy(e).to(ctx.device)
             return torch.from_numpy(r).to(ctx.device), torch.from_numpy(e).to(ctx.device)
 
-        def predict(state: Tuple[torch.Tensor, torch.Tensor], X: Any, ctx: WorkerContext) -> Dict[str, np.ndarray]:
+        def predict(state: Tuple[Any, torch.Tensor], X: Any, ctx: WorkerContext) -> Dict[str, np.ndarray]:
             from .core.base import to_device
             from .models.umap import umap_transform
 
             Rd, Ed = state
-            Xd = to_device(np.asarray(X, dtype=np.float32), ctx.device, torch.float32)
+            if sparse:
+                import scipy.sparse as sp
+
+                # sparse-vector partitions arrive CSR; dense vectors and arrays are converted on the host
+                Xh = _host_csr(X if sp.issparse(X) else np.asarray(X, dtype=np.float32))
+                if Xh.shape[1] != Rd.shape[1]:
+                    raise ValueError("transform: %d features, the model was fitted on %d" % (Xh.shape[1], Rd.shape[1]))
+                Xd = to_device(Xh, ctx.device, torch.float32)
+            else:
+                Xd = to_device(np.asarray(X, dtype=np.float32), ctx.device, torch.float32)
             return {out_col: umap_transform(Xd, Rd, Ed, params)}
 
         return construct, predict
@@ -419,6 +575,11 @@ class UMAPModel(UMAPClass, _Model, _UMAPParams):
     def _transform(self, dataset: Any) -> Any:
         from .parallel.spark import is_spark_dataframe, spark_transform
 
+        if is_spark_dataframe(dataset) and self._sparse_fitted():
+            raise NotImplementedError(
+                "transform of a pyspark DataFrame by a sparse-fitted UMAPModel is not implemented: the Spark transform "
+                "broadcasts row chunks of a dense raw_data_. Transform an in-process DataFrame / pandas frame, or fit "
+                "with enable_sparse_data_optim=False.")
         if is_spark_dataframe(dataset):
             # per-partition transform (kNN to the training rows + SGD placement); like the reference
             # the output holds the features and the embedding only (umap.py:1149-1241)
