@@ -27,6 +27,28 @@ def _share(total: int, rank: int, world: int) -> Tuple[int, int]:
     return int(b[rank]), int(b[rank + 1])
 
 
+def _prepare(X: torch.Tensor, eps: float, metric: str) -> Tuple[torch.Tensor, torch.Tensor, float]:
+    """(rows, their squared norms, squared threshold) the tile sweeps run on; X is the full matrix.
+
+    euclidean: the rows minus their column mean. DBSCAN is translation invariant, the expanded form
+    ||a||^2 + ||b||^2 - 2 a.b of the sweeps is not: its fp32 error grows with the norms, so they are
+    taken about the data's own centre. Every rank holds the same matrix and reduces it in the same
+    order, so the centre is the same on every rank.
+    cosine: unit rows, ||a - b||^2 = 2 (1 - cos). An all-zero row stays zero and gets the norm 1, so it
+    is at ||0||^2 + ||b||^2 - 0 = 2, cosine distance 1, from every row but itself (sklearn's rule)."""
+    if metric == "cosine":
+        nrm = X.norm(dim=1, keepdim=True)
+        X = X / nrm.clamp_min(1e-30)
+        xn = ops.row_sqnorm(X)
+        xn = torch.where(nrm.view(-1) == 0, torch.ones_like(xn), xn)
+        return X, xn, 2.0 * float(eps)
+    if metric in ("euclidean", "l2"):
+        if X.shape[0]:
+            X = (X - X.mean(0, dtype=torch.float64).float()).contiguous()
+        return X, ops.row_sqnorm(X), float(eps) ** 2
+    raise ValueError("Unsupported metric %r for DBSCAN" % metric)
+
+
 def dbscan_fit_predict(X_local: torch.Tensor, ctx: WorkerContext, eps: float, min_samples: int,
                        metric: str = "euclidean") -> Tuple[np.ndarray, np.ndarray]:
     """(labels of this rank's rows, core-sample flags of this rank's rows)."""
@@ -35,14 +57,7 @@ def dbscan_fit_predict(X_local: torch.Tensor, ctx: WorkerContext, eps: float, mi
     start = sum(sizes[: ctx.rank])
     X = torch.cat([p.to(X_local.device) for p in parts], 0).contiguous()
     N = X.shape[0]
-    if metric == "cosine":
-        X = X / X.norm(dim=1, keepdim=True).clamp_min(1e-30)
-        eps2 = 2.0 * float(eps)  # ||a - b||^2 = 2 (1 - cos) for unit rows
-    elif metric in ("euclidean", "l2"):
-        eps2 = float(eps) ** 2
-    else:
-        raise ValueError("Unsupported metric %r for DBSCAN" % metric)
-    xn = ops.row_sqnorm(X)
+    X, xn, eps2 = _prepare(X, eps, metric)
     t0, t1 = _share(ops.dbscan_num_tiles(N), ctx.rank, ctx.world_size)
     counts = ops.dbscan_degree(X, xn, eps2, t0, t1)
     ctx.comm.allreduce(counts)

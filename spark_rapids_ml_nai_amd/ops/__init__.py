@@ -2835,6 +2835,8 @@ def _db_tiles(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: in
         A, B = X[r0: r0 + DB_TILE].float(), X[c0: c0 + DB_TILE].float()
         d = (xnorm[r0: r0 + DB_TILE].float().view(-1, 1) + xnorm[c0: c0 + DB_TILE].float().view(1, -1)
              - 2.0 * (A @ B.T)).clamp_min(0)
+        if bi == bj:
+            d.fill_diagonal_(0.0)  # like the kernel: the self pair is a neighbour at every eps >= 0
         yield bi == bj, r0, c0, torch.where(d <= eps2, d, torch.full_like(d, float("inf")))
 
 

@@ -2,7 +2,8 @@
 //
 // The N x N eps-adjacency is never materialised. Both passes sweep the lower triangle of 128 x 128
 // tile pairs (bj <= bi, a rank owns a contiguous range of that linear tile index) and recompute the
-// tile's distances on MFMA (||a||^2 + ||b||^2 - 2 a.b, fp32):
+// tile's distances on MFMA (||a||^2 + ||b||^2 - 2 a.b, fp32; the self pair is 0 by rule). The fp32 error
+// of that form grows with the norms: callers pass rows taken about their own centre (models/dbscan.py).
 //   srml_dbscan_degree_f32: eps-degree of every row (self included); each tile counts its rows
 //     and, off the diagonal, its columns (symmetry) -> one global atomicAdd per row / column.
 //   srml_dbscan_link_f32: connected components of the core points. Inside a tile the core-core
@@ -51,7 +52,8 @@ __device__ __forceinline__ void distance_tile(const float* __restrict__ X, long 
         const int rl = acc_row(mt, r);
         const long gr = r0 + rl;
         const float rn = gr < N ? xnorm[gr] : 0.f;
-        const float d = fmaxf(fmaf(-2.f, acc[mt][nt][r], rn + cn), 0.f);
+        // a point is its own neighbour at every eps >= 0: the expanded form of D(i, i) is rounding noise
+        const float d = gr == gc ? 0.f : fmaxf(fmaf(-2.f, acc[mt][nt][r], rn + cn), 0.f);
         sm.D[rl][cl] = (gr < N && gc < N && d <= eps2) ? d : __builtin_huge_valf();
       }
   }
