@@ -571,7 +571,7 @@ def grow_forest(bins: torch.Tensor, edges_h: np.ndarray, y: torch.Tensor, ctx: W
     call_seed = int(torch.randint(0, 1 << 62, (1,), generator=gen, device=dev).item())
     bins_il = None
     bins_rm: Optional[torch.Tensor] = None
-    # packed cells need every item's weights <= 2^20: rows per item (<= WIDE_ROWS_MAX) x max weight
+    # packed cells need every item's weights < 2^20: rows per item (<= WIDE_ROWS_MAX) x max weight
     pack_scale = None
     if (regression and RF_PACK and dev.type == "cuda" and IL_KERNEL == "wide" and not deterministic()
             and float(wpos.max().item()) * WIDE_ROWS_MAX <= ops.RF_PACK_MAX_WEIGHT):

@@ -1258,7 +1258,7 @@ def rf_hist_fb_wide(B: int, S: int, regression: bool, packed: bool = False) -> i
 
 
 RF_PACK_BITS = 22  # |rint(y * scale)| <= 2^22 (csrc/forest.hip RF_PACK_BIAS)
-RF_PACK_MAX_WEIGHT = float(1 << 20)  # per work item: (sum w) << 44 must not overflow
+RF_PACK_MAX_WEIGHT = float((1 << 20) - 1)  # per work item: the count field is bits 44..63, sum w < 2^20
 
 
 def rf_pack_scale(y: torch.Tensor) -> float:
@@ -1336,7 +1336,7 @@ def rf_hist(bins: torch.Tensor, idx: torch.Tensor, label: torch.Tensor, wcnt: Op
     records of ``rec_bytes`` (the value ``bins_il`` was built with). ``packed_scale`` (wide
     regression, not deterministic): one u64 LDS cell per (feature, bin) holding the weighted count
     and the sum of w * rint(y * packed_scale), packed_scale = 2^22 / max|y| (``rf_pack_scale``);
-    the caller keeps the weights of one item <= 2^20. ``out``: a zeroed / partly accumulated
+    the caller keeps the weights of one item below 2^20 (``RF_PACK_MAX_WEIGHT``). ``out``: a zeroed / partly accumulated
     histogram the items ADD into (no single-chunk stores: ``exclusive`` must be None) — a histogram
     built over several launches, e.g. one per streamed row chunk; ``wy``: the (weight, label) pairs
     in ``idx`` order from an earlier call (``rf_hist_wy``)."""

@@ -415,9 +415,10 @@ __device__ __forceinline__ int rec_pick(uint4 a, uint4 b, uint4 c, uint4 d, int 
 // PACK (regression, non-deterministic): ONE u64 LDS atomic per (row, feature) instead of a u32
 // count + u64 sum: cell = (sum w) << 44 | sum w (yq + 2^22), yq = rint(y * yscale) with yscale =
 // 2^22 / max|y| (|yq| <= 2^22, so every addend's low field is in [0, w 2^23] and never borrows);
-// with sum w <= 2^20 per block (rows per item x max weight, checked by the host) the low field
-// stays below 2^43. Count exact; sum quantised to 2^-22 max|y| per row (fp32-level), unpacked at
-// the flush. Two LDS words per cell instead of three: ~1.5x the features per block.
+// with sum w < 2^20 per block (rows per item x max weight, checked by the host: the count field
+// is the 20 bits 44..63, so 2^20 itself would wrap to 0) the low field stays below 2^43. Count
+// exact; sum quantised to 2^-22 max|y| per row (fp32-level), unpacked at the flush. Two LDS words
+// per cell instead of three: ~1.5x the features per block.
 constexpr int RF_PACK_SHIFT = 44;
 constexpr long long RF_PACK_BIAS = 1LL << 22;
 
@@ -568,7 +569,7 @@ SRML_API int srml_rf_hist_wide(const unsigned char* rec, long m, const int* idx,
                                int n_items, const int* node_feats, int nf, int B, int S, int regression, double yscale,
                                int fbw, int fixed, int rb, unsigned* hist_u, double* hist_d, hipStream_t stream) {
   // fixed: 1 = deterministic i64 cells, 2 = packed count/sum cells (yscale = 2^22 / max|y|; the
-  // caller guarantees sum w <= 2^20 per item)
+  // caller guarantees sum w < 2^20 per item)
   if (n_items <= 0) return 0;
   if (regression && S != 2) return -6;
   if (fbw < 1 || (reinterpret_cast<uintptr_t>(rec) & 15)) return -7;
