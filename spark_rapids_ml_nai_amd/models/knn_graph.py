@@ -11,6 +11,10 @@
   1/W of the training sample per rank (cluster sums all-reduced), each rank buckets its 1/W of
   the rows (labels all-gathered) and takes a contiguous, work-balanced range of query tiles.
 
+* ``knn_graph_csr_approx`` — approximate, CSR rows only (``build_algo="rp_nn_descent"``): candidates
+  from a dense graph of a seeded random projection of the rows, then NN-descent rounds on the CSR
+  rows in the route's own metric (``ops.csr_nnd_join``).
+
 The reference fits UMAP on one GPU with cuML's own kNN (``umap.py:840-850,924-958``).
 """
 from __future__ import annotations
@@ -473,6 +477,102 @@ def knn_graph_ivf(X: torch.Tensor, k: int, nlist: Optional[int] = None, nprobe: 
     return dist, out_i
 
 
+RP_PROJ_DIM = 64       # columns of the random projection of build_algo="rp_nn_descent"
+RP_PROJ_DIM_MAX = 128  # the dense pair kernel's row width (ops.knn_lists_f16_ok)
+RP_ALGO = "rp_nn_descent"
+
+
+def reverse_lists(pos: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(perm int64 [N kw], off int64 [N + 1]): the N kw edges of the graph ``pos`` grouped by target,
+    stable (the source order is kept). Padding edges (-1) are edges to nobody: out of [0, N) they
+    trail after off[N] / lead before off[0]."""
+    N = pos.shape[0]
+    tgt = pos.reshape(-1)
+    if tgt.is_cuda and N <= int(ops.native.lib().srml_label_sort_kmax()):
+        perm, off, _ = ops.label_sort(tgt.int(), N)
+        return perm.long(), off
+    srt, perm = torch.sort(tgt, stable=True)
+    return perm, torch.searchsorted(srt, torch.arange(N + 1, device=pos.device, dtype=srt.dtype))
+
+
+def csr_projection_rows(P: Any, kind: str) -> Any:
+    """The prepared CSR rows ``P`` with the values the random projection reads: the prepared values
+    (Euclidean kinds: cosine rows arrive unit-scaled; hellinger: the square roots), for jaccard the
+    indicators scaled by 1 / sqrt(nnz) (unit rows whose dot is the overlap share; empty rows stay zero)."""
+    from ..core.base import CSR
+
+    data = P.data
+    if kind == "jaccard":
+        scale = torch.where(P.aux > 0, torch.rsqrt(P.aux.clamp_min(1.0)), torch.zeros_like(P.aux))
+        data = (data * torch.repeat_interleave(scale, P.indptr[1:] - P.indptr[:-1])).contiguous()
+    return CSR(indptr=P.indptr, indices=P.indices, data=data, shape=P.shape)
+
+
+def knn_graph_csr_approx(X: Any, k: int, metric: str = "euclidean", seed: int = 0, ctx: Any = None,
+                         phases: Optional[dict] = None, proj_dim: Optional[int] = None,
+                         nnd_iters: Optional[int] = None, a: int = 8, b: int = 8, R: int = 16,
+                         dense_kwds: Optional[dict] = None, cand_k: Optional[int] = None,
+                         rounds: Optional[list] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Approximate all-points graph of CSR rows: (distances [N, k] fp32, indices [N, k] int64).
+
+    1. candidates: P = A G for a seeded Gaussian G (n x ``proj_dim``; rank 0's under a ``ctx``),
+       ``build_knn_graph(P, cand_k, "auto", dense_kwds)`` on the dense P (exact up to 100 000 rows,
+       per-query-probed IVF lists beyond). Only the neighbour ids are kept (``cand_k``: k);
+    2. round 0 re-scores the candidates on the CSR rows in the route's own metric (the join with
+       a = 0, R = 0), so every distance that leaves here comes from the CSR rows;
+    3. ``nnd_iters`` NN-descent rounds follow (``nn_descent_refine``'s candidate set: own list,
+       first ``a`` neighbours' first ``b`` neighbours, up to ``R`` reverse neighbours), each one
+       ``ops.csr_nnd_join`` launch. Distributed, every rank refines its ``row_split`` block of the
+       replicated graph and the blocks are all-gathered after every round.
+
+    ``rounds`` (a list) receives ("candidates", None, ids) and then (name, keys, ids) of the whole
+    graph after round 0 and every later round.
+    Rows short of k candidates (tiny IVF lists) end with -1 at the row's largest distance."""
+    import time
+
+    kind = sparse_kind(metric)
+    N, n = X.shape
+    dev = X.data.device
+    proj_dim = RP_PROJ_DIM if proj_dim is None else int(proj_dim)
+    if not 1 <= proj_dim <= RP_PROJ_DIM_MAX:
+        raise ValueError("proj_dim=%d outside [1, %d]" % (proj_dim, RP_PROJ_DIM_MAX))
+    nnd_iters = NND_ITERS if nnd_iters is None else int(nnd_iters)
+    t0 = time.perf_counter()
+    name = "sqeuclidean" if kind == "euclidean" else kind
+    P = ops.csr_prepare(X, name)
+    G = torch.randn((n, proj_dim), generator=torch.Generator(device=dev).manual_seed(int(seed)), device=dev)
+    dist = ctx is not None and ctx.world_size > 1
+    if dist:
+        ctx.comm.broadcast(G, src=0)  # device generators may differ between ranks' devices
+    Z = ops.csr_spmm(csr_projection_rows(P, kind), G).contiguous()
+    t0 = record_phase(phases, "rp_projection", N, t0, dev)
+    kc = max(1, min(int(cand_k) if cand_k else k, N))
+    sub: dict = {}
+    _, cand = build_knn_graph(Z, kc, "auto", dense_kwds, seed, ctx, phases=sub)
+    lo, hi = row_split(N, ctx)
+    t0 = record_phase(phases, "rp_candidates", hi - lo, t0, dev)
+    if phases is not None:
+        phases.update({"rp_candidates." + key: val for key, val in sub.items()})
+    Q = P.rows(lo, hi)
+    if rounds is not None:
+        rounds.append(("candidates", None, cand))
+    keys, pos = ops.csr_nnd_join(Q, P, cand, None, None, k, 0, 0, 0, name, row0=lo)
+    keys, pos = gather_rows(keys, ctx), gather_rows(pos, ctx)
+    if rounds is not None:
+        rounds.append(("round0", keys, pos))
+    for it in range(max(0, nnd_iters)):
+        perm, off = reverse_lists(pos)
+        keys, pos = ops.csr_nnd_join(Q, P, pos, perm, off, k, a, b, R, name, row0=lo)
+        keys, pos = gather_rows(keys, ctx), gather_rows(pos, ctx)
+        if rounds is not None:
+            rounds.append(("round%d" % (it + 1), keys, pos))
+    record_phase(phases, "csr_nn_descent", hi - lo, t0, dev)
+    fin = torch.isfinite(keys)
+    rowmax = torch.where(fin, keys, torch.zeros_like(keys)).max(1, keepdim=True).values
+    keys = torch.where(fin, keys, rowmax)
+    return (torch.sqrt(keys.clamp_min(0)) if kind == "euclidean" else keys), pos
+
+
 def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Optional[dict] = None,
                     seed: int = 0, ctx: Any = None, list_order: bool = False, phases: Optional[dict] = None,
                     metric: str = "euclidean", p: float = 2.0) -> Any:
@@ -485,20 +585,35 @@ def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Option
     NN-descent re-scoring are Euclidean throughout, so ``ivf`` / ``nn_descent`` raise.
 
     A CSR ``X`` (metric kinds ``euclidean`` — the caller may have unit-scaled the rows for cosine —
-    ``hellinger`` and ``jaccard``) is served by the exact CSR search only, at any row count too."""
+    ``hellinger`` and ``jaccard``) is served by the exact CSR search (``auto``, ``brute_force_knn``; at
+    any row count too) or by ``rp_nn_descent`` (``knn_graph_csr_approx``; ``build_kwds`` ``proj_dim``,
+    ``nnd_iters``, ``a``, ``b``, ``R``, and ``nlist`` / ``nprobe`` / ``probe`` for the dense candidate
+    build). ``rp_nn_descent`` serves CSR rows only."""
     algo = (build_algo or "auto").lower()
+    if algo == RP_ALGO and not is_csr(X):
+        raise ValueError("build_algo %r builds graphs of sparse (CSR) rows only; dense rows have 'ivf' and "
+                         "'nn_descent'" % (build_algo,))
     if is_csr(X):
-        sparse_kind(metric)
+        kind = sparse_kind(metric)
         if algo in ("ivf", "ivfflat", "ivf_flat", "nn_descent"):
             raise ValueError("build_algo %r builds graphs of dense rows only; sparse (CSR) rows need build_algo "
-                             "'auto' or 'brute_force_knn' (the exact search)" % (build_algo,))
+                             "'auto' or 'brute_force_knn' (the exact search), or 'rp_nn_descent' (approximate)"
+                             % (build_algo,))
+        if algo == RP_ALGO:
+            kw = dict(build_kwds or {})
+            dense_kwds = {key: kw[key] for key in ("nlist", "nprobe", "probe") if kw.get(key) is not None}
+            d, i = knn_graph_csr_approx(X, k, kind, seed=seed, ctx=ctx, phases=phases, proj_dim=kw.get("proj_dim"),
+                                        nnd_iters=kw.get("nnd_iters"), a=int(kw.get("a", 8)), b=int(kw.get("b", 8)),
+                                        R=int(kw.get("R", 16)), dense_kwds=dense_kwds, cand_k=kw.get("cand_k"))
+            return (d, i, None) if list_order else (d, i)
         if algo == "auto":
             algo = "brute_force_knn"
         if X.shape[0] > BRUTE_MAX_ROWS:
             from ..utils.log import get_logger
 
-            get_logger("knn_graph").info("sparse kNN graph of %d rows: the CSR search is exact and O(N^2) (no "
-                                         "approximate builder for sparse rows)", X.shape[0])
+            get_logger("knn_graph").info("sparse kNN graph of %d rows: the CSR search is exact and O(N^2); "
+                                         "build_algo='rp_nn_descent' builds an approximate graph of sparse rows",
+                                         X.shape[0])
     elif not is_euclidean(metric):
         if algo in ("ivf", "ivfflat", "ivf_flat", "nn_descent"):
             raise ValueError("build_algo %r builds Euclidean graphs only; metric %r needs build_algo 'auto' or "
@@ -521,4 +636,5 @@ def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Option
         nnd = int(kw.get("nnd_iters", NND_ITERS)) if algo == "nn_descent" else int(kw.get("nnd_iters", 0))
         return knn_graph_ivf(X, k, nlist=kw.get("nlist"), nprobe=kw.get("nprobe"), seed=seed, ctx=ctx,
                              list_order=list_order, phases=phases, probe=kw.get("probe"), nnd_iters=nnd)
-    raise ValueError("Unsupported build_algo %r (auto, brute_force_knn, ivf, nn_descent)" % build_algo)
+    raise ValueError("Unsupported build_algo %r (auto, brute_force_knn, ivf, nn_descent; rp_nn_descent for sparse "
+                     "rows)" % build_algo)

@@ -3773,6 +3773,191 @@ def csr_refine_sort(Q: Any, I: Any, ids: torch.Tensor) -> Tuple[torch.Tensor, to
 
 
 # ------------------------------------------------------------------------------------------
+# NN-descent join on CSR rows (csrc/csr_nnd.hip): the approximate sparse graph of UMAP
+# dispatch constants of csrc/csr_nnd.hip (srml_csr_nnd_config returns the same three)
+CSR_NND_CAND_CAP = 512      # candidate slots kw + a b + R of one row (NJ_CAND)
+CSR_NND_LDS_CAP = 2048      # query non-zeros the join kernel stages in LDS (NJ_CAP)
+CSR_NND_KMAX = 64           # widest output list (NJ_KMAX)
+_CSR_NND_TORCH_TERMS = 1 << 23  # (pair, non-zero) terms of one chunk of the torch form
+
+
+def csr_nnd_candidates(pos: torch.Tensor, perm: Optional[torch.Tensor], off: Optional[torch.Tensor], r0: int, r1: int,
+                       a: int, b: int, R: int) -> torch.Tensor:
+    """The candidate slots of graph rows r0 .. r1 as the join kernel gathers them, int64
+    [r1 - r0, kw + a b + R]: ``pos[i]``, ``pos[pos[i, :a], :b]`` and the first R entries of row i's
+    reverse list ``perm[off[i] : off[i + 1]] // kw``; empty slots and ids outside [0, N) are -1."""
+    N, kw = pos.shape
+    own = pos[r0:r1]
+    parts = [own]
+    if a * b > 0:
+        nb = own[:, :a]
+        ok = (nb >= 0) & (nb < N)
+        non = pos.index_select(0, nb.clamp(0, N - 1).reshape(-1))[:, :b].reshape(r1 - r0, a * b)
+        parts.append(torch.where(ok.repeat_interleave(b, 1), non, torch.full_like(non, -1)))
+    if R > 0:
+        st = off[r0:r1].unsqueeze(1) + torch.arange(R, device=pos.device)
+        ok = (st < off[r0 + 1: r1 + 1].unsqueeze(1)) & (st < perm.numel())
+        rev = perm[st.clamp(0, max(0, perm.numel() - 1))] // kw if perm.numel() else torch.full_like(st, -1)
+        parts.append(torch.where(ok, rev, torch.full_like(st, -1)))
+    cand = torch.cat(parts, 1)
+    return torch.where((cand >= 0) & (cand < N), cand, torch.full_like(cand, -1))
+
+
+def _csr_segments(starts: torch.Tensor, lens: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(segment number, element index) of every element of the runs starts[s] .. starts[s] + lens[s]."""
+    seg = torch.repeat_interleave(torch.arange(lens.numel(), device=lens.device), lens)
+    first = torch.cumsum(lens, 0) - lens
+    return seg, starts[seg] + torch.arange(seg.numel(), device=lens.device) - first[seg]
+
+
+class _CSRKeyed:
+    """The non-zeros of a row block under the sorted key row * n + column (rows are in order and
+    columns increase within a row, so the keys ascend): a (row, column) lookup is one binary search."""
+
+    def __init__(self, A: CSRRows) -> None:
+        m, n = A.shape
+        a = int(A.indptr[0]) if m else 0
+        cnt = A.indptr[1:] - A.indptr[:-1]
+        rows = torch.repeat_interleave(torch.arange(m, device=cnt.device), cnt)
+        self.n = n
+        self.keys = rows * n + A.indices[a: a + rows.numel()].long()
+        self.vals = A.data[a: a + rows.numel()].double()
+
+    def find(self, rows: torch.Tensor, cols: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(hit, value or 0) of the entries (rows[e], cols[e])."""
+        want = rows * self.n + cols
+        if not self.keys.numel():
+            z = torch.zeros(want.shape, dtype=torch.float64, device=want.device)
+            return z > 0, z
+        p = torch.searchsorted(self.keys, want).clamp_max(self.keys.numel() - 1)
+        hit = self.keys[p] == want
+        return hit, torch.where(hit, self.vals[p], torch.zeros_like(self.vals[p]))
+
+
+def _csr_nnd_keys_torch(Qp: CSRRows, Ip: CSRRows, qk: _CSRKeyed, ik: _CSRKeyed, qrow: torch.Tensor,
+                        ids: torch.Tensor) -> torch.Tensor:
+    """fp32 keys of the pairs (query row qrow[p] of the block, item ids[p]) in the join kernel's forms,
+    accumulated in fp64 over the non-zeros only: direct-form squared distances (every (x_j - y_j)^2
+    over the union of the supports), sqrt(max(0, 1 - S)) and the fp32 Jaccard expression."""
+    dev = qrow.device
+    P = qrow.numel()
+    ys, yl = Ip.indptr[ids], Ip.indptr[ids + 1] - Ip.indptr[ids]
+    seg, e = _csr_segments(ys, yl)
+    cols, yv = Ip.indices[e].long(), Ip.data[e].double()
+    _, xv = qk.find(qrow[seg], cols)
+    acc = torch.zeros(P, dtype=torch.float64, device=dev)
+    if Qp.metric != "sqeuclidean":
+        S = acc.index_add_(0, seg, xv * yv)
+        if Qp.metric == "hellinger":
+            return torch.sqrt((1.0 - S).clamp_min(0).float())
+        S = S.float()
+        uni = Qp.aux[qrow].float() + Ip.aux[ids].float() - S
+        return torch.where(uni > 0, (uni - S) / uni.clamp_min(1e-30), torch.zeros_like(uni))
+    acc.index_add_(0, seg, (xv - yv) ** 2)
+    xs, xl = Qp.indptr[qrow], Qp.indptr[qrow + 1] - Qp.indptr[qrow]
+    seg, e = _csr_segments(xs, xl)
+    hit, _ = ik.find(ids[seg], Qp.indices[e].long())
+    xv = Qp.data[e].double()
+    acc.index_add_(0, seg, torch.where(hit, torch.zeros_like(xv), xv * xv))
+    return acc.float()
+
+
+def _csr_nnd_join_torch(Qp: CSRRows, Ip: CSRRows, pos: torch.Tensor, perm: Optional[torch.Tensor],
+                        off: Optional[torch.Tensor], k: int, a: int, b: int, R: int,
+                        row0: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    N = pos.shape[0]
+    rows, dev = Qp.shape[0], pos.device
+    C = pos.shape[1] + a * b + R
+    qk, ik = _CSRKeyed(Qp), _CSRKeyed(Ip)
+    # rows of a chunk: about _CSR_NND_TORCH_TERMS (pair, non-zero) terms at the mean row lengths
+    mean_q = (int(Qp.indptr[-1]) - int(Qp.indptr[0])) // max(1, rows) if rows else 0
+    mean_i = (int(Ip.indptr[-1]) - int(Ip.indptr[0])) // max(1, N) if N else 0
+    step = max(1, _CSR_NND_TORCH_TERMS // (C * max(1, mean_q + mean_i)))
+    outk, outi = [], []
+    s = 0
+    while s < rows:
+        e = min(rows, s + step)
+        cand = csr_nnd_candidates(pos, perm, off, row0 + s, row0 + e, a, b, R)
+        cand = torch.sort(torch.where(cand >= 0, cand, torch.full_like(cand, N)), dim=1).values  # empty slots trail
+        dup = torch.zeros_like(cand, dtype=torch.bool)
+        dup[:, 1:] = cand[:, 1:] == cand[:, :-1]
+        cand = torch.sort(torch.where(dup, torch.full_like(cand, N), cand), dim=1).values
+        live = cand < N
+        qrow = torch.arange(s, e, device=dev).view(-1, 1).expand_as(cand)[live]
+        keys = torch.full(cand.shape, float("inf"), dtype=torch.float32, device=dev)
+        keys[live] = _csr_nnd_keys_torch(Qp, Ip, qk, ik, qrow, cand[live])
+        # the ids ascend within a row and the dropped slots (id N) trail: one stable sort by key
+        # orders by (key, id) and leaves a dropped slot after every live one, +inf keys included
+        keys2, j = torch.sort(keys, dim=1, stable=True)
+        cand = cand.gather(1, j)
+        kk = min(k, C)
+        vk = torch.full((e - s, k), float("inf"), dtype=torch.float32, device=dev)
+        vi = torch.full((e - s, k), -1, dtype=torch.int64, device=dev)
+        vk[:, :kk] = keys2[:, :kk]
+        vi[:, :kk] = torch.where(cand[:, :kk] < N, cand[:, :kk], torch.full_like(cand[:, :kk], -1))
+        outk.append(vk)
+        outi.append(vi)
+        s = e
+    if not outk:
+        return (torch.empty((0, k), dtype=torch.float32, device=dev), torch.empty((0, k), dtype=torch.int64, device=dev))
+    return torch.cat(outk), torch.cat(outi)
+
+
+def csr_nnd_join(Q_rows: Any, I: Any, pos: torch.Tensor, perm: Optional[torch.Tensor], off: Optional[torch.Tensor],
+                 k: int, a: int, b: int, R: int, metric: str, row0: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One NN-descent join on CSR rows: for every row of the block ``Q_rows`` (graph rows ``row0 ..
+    row0 + rows`` of ``I``'s all-points graph ``pos``, int64 [N, kw]) the ``k`` nearest among its own
+    list, its first ``a`` neighbours' first ``b`` neighbours and up to ``R`` reverse neighbours
+    (``perm`` / ``off``: the N kw edges grouped by target, as ``label_sort`` returns them), re-ranked
+    by the metric of the CSR rows: (keys fp32 [rows, k], ids int64 [rows, k]) ascending by
+    (key, id), equal keys to the lower id, missing places +inf / -1. -1 entries are dropped and
+    the ids de-duplicated before any distance is computed; a row that lists itself keeps itself at
+    its true distance. Keys: ``sqeuclidean`` squared distances in direct form, ``hellinger`` and
+    ``jaccard`` the distances (``csr_prepare``'s table). ``a`` and ``b`` are cut to the list width.
+
+    fp32 device rows within the kernel's limits (k <= ``CSR_NND_KMAX``, kw + a b + R <=
+    ``CSR_NND_CAND_CAP``) run ``srml_csr_nnd_join_f32``: one workgroup per row, no atomics, the
+    output a pure function of the inputs. Anything else runs a torch form of the same contract."""
+    Qp, Ip = _csr_pair(Q_rows, I, metric)
+    if pos.dim() != 2 or pos.shape[0] != Ip.shape[0] or pos.shape[1] < 1:
+        raise ValueError("csr_nnd_join: the graph must be [%d, kw >= 1], got %s" % (Ip.shape[0], tuple(pos.shape)))
+    N, kw = pos.shape
+    rows, row0, k = Qp.shape[0], int(row0), int(k)
+    if k < 1:
+        raise ValueError("csr_nnd_join: k=%d" % k)
+    if row0 < 0 or row0 + rows > N:
+        raise ValueError("csr_nnd_join: rows %d .. %d outside the graph's %d rows" % (row0, row0 + rows, N))
+    a, b, R = max(0, min(int(a), kw)), max(0, min(int(b), kw)), max(0, int(R))
+    if a * b == 0:
+        a = b = 0
+    pos = _c(pos.to(torch.int64))
+    if R > 0:
+        if perm is None or off is None or perm.numel() != N * kw or off.numel() != N + 1:
+            raise ValueError("csr_nnd_join: R > 0 needs perm (N kw edges) and off (N + 1 starts)")
+        perm, off = _c(perm.to(torch.int64)), _c(off.to(torch.int64))
+    else:
+        perm = off = None
+    dev = Qp.device
+    if not (rows and _csr_native(Qp, Ip) and pos.is_cuda and k <= CSR_NND_KMAX and kw + a * b + R <= CSR_NND_CAND_CAP
+            and N < 2 ** 31 - 1):
+        return _csr_nnd_join_torch(Qp, Ip, pos, perm, off, k, a, b, R, row0)
+    outk = torch.empty((rows, k), dtype=torch.float32, device=dev)
+    outi = torch.empty((rows, k), dtype=torch.int64, device=dev)
+    rc = native.call_status("srml_csr_nnd_join_f32", _c(Qp.indptr).data_ptr(), Qp.indices.data_ptr(),
+                            Qp.data.data_ptr(), Qp.aux.data_ptr() if Qp.aux is not None else None, rows, row0,
+                            _c(Ip.indptr).data_ptr(), Ip.indices.data_ptr(), Ip.data.data_ptr(),
+                            Ip.aux.data_ptr() if Ip.aux is not None else None, N, pos.data_ptr(), kw,
+                            perm.data_ptr() if perm is not None else None, off.data_ptr() if off is not None else None,
+                            k, a, b, R, CSR_KNN_CODES[Qp.metric], outk.data_ptr(), outi.data_ptr(), native.stream(dev))
+    if rc < 0:
+        raise ValueError("srml_csr_nnd_join_f32 refused the launch (status %d: -1 grid overflow, -2 metric / "
+                         "arguments, -3 candidate slots, -9 LDS)" % rc)
+    if rc != 0:
+        raise RuntimeError("srml_csr_nnd_join_f32 launch failed with HIP status %d" % rc)
+    return outk, outi
+
+
+# ------------------------------------------------------------------------------------------
 # Logistic loss + gradient accumulation for the on-device quasi-Newton driver (models/qn.py)
 def _is_csr(X) -> bool:
     return hasattr(X, "indptr") and hasattr(X, "indices")

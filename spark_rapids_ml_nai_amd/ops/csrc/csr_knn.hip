@@ -35,6 +35,7 @@
 //                  exact integer in fp32)                   aux = row non-zero counts
 // Cosine is the sqeuclidean key of unit rows (the caller scales the values).
 #include "common.h"
+#include "csr_pair.h"  // ck_lower_bound, rf_pair
 
 namespace {
 enum : int { CK_SQEUCLIDEAN = 0, CK_HELLINGER = 1, CK_JACCARD = 2 };
@@ -50,17 +51,6 @@ constexpr int CK_LDS_MAX = 160 * 1024;
 
 constexpr int RF_T = 256;      // refine: 4 waves per query
 constexpr int RF_CAP = 2048;   // query non-zeros staged in LDS (index + value: 16 KiB)
-
-// first position in [lo, hi) of the sorted idx with idx[pos] >= key
-template <typename P>
-__device__ __forceinline__ long ck_lower_bound(P idx, long lo, long hi, int key) {
-  while (lo < hi) {
-    const long mid = (lo + hi) >> 1;
-    if (idx[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ long ck_shfl(long v, int src) {
   const int lo = __shfl((int)(v & 0xffffffffL), src, 64);
@@ -184,31 +174,6 @@ int ck_launch(const long* qptr, const int* qidx, const float* qval, const float*
   hipLaunchKernelGGL((csr_pairdist_kernel<M>), dim3((unsigned)(nq * ni)), dim3(CK_T), CK_LDS, stream, qptr, qidx, qval,
                      qaux, r, iptr, iidx, ival, iaux, L, n, D, ldd, (int)ni);
   return srml_status();
-}
-
-// squared distance of x (nx non-zeros at xi / xv, an LDS or a global pointer) and y, summed by
-// one wave: the lanes stride y and look each column up in x, then stride x for the columns y lacks
-template <typename PI, typename PV>
-__device__ __forceinline__ float rf_pair(PI xi, PV xv, long nx, const int* __restrict__ yi,
-                                         const float* __restrict__ yv, long ny, int lane) {
-  float sum = 0.f;
-  for (long p = lane; p < ny; p += 64) {
-    const int c = yi[p];
-    const float y = yv[p];
-    const long pos = ck_lower_bound(xi, 0, nx, c);
-    const float x = (pos < nx && xi[pos] == c) ? xv[pos] : 0.f;
-    const float d = x - y;
-    sum = fmaf(d, d, sum);
-  }
-  for (long p = lane; p < nx; p += 64) {
-    const int c = xi[p];
-    const long pos = ck_lower_bound(yi, 0, ny, c);
-    if (!(pos < ny && yi[pos] == c)) {
-      const float x = xv[p];
-      sum = fmaf(x, x, sum);
-    }
-  }
-  return wave_sum(sum);
 }
 
 __global__ __launch_bounds__(RF_T) void csr_refine_kernel(const long* __restrict__ qptr, const int* __restrict__ qidx,

@@ -212,6 +212,11 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_csr_knn_config": (_I,),
     "srml_csr_pairdist_f32": (_P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _I, _I, _P, _L, _P),
     "srml_csr_refine_f32": (_P, _P, _P, _L, _P, _P, _P, _L, _P, _I, _L, _P, _L, _P),
+    # NN-descent join on CSR rows: query block (offsets, indices, values, aux, rows, row0), item matrix
+    # (offsets, indices, values, aux, N), graph (pos, kw, perm, off), k, a, b, R, metric, out keys / ids
+    "srml_csr_nnd_config": (_I,),
+    "srml_csr_nnd_join_f32": (_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P,
+                              _P),
     "srml_confusion_counts": (_P, _I, _P, _I, _L, _I, _P, _P),
     "srml_logloss_sum": (_P, _I, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_reg_moments": (_P, _I, _P, _I, _L, _P, _P),

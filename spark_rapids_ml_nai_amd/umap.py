@@ -104,9 +104,14 @@ class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatures
     sample_fraction = _p("sample_fraction", "Fraction of the dataset used for fitting.", TypeConverters.toFloat)
     build_algo = _p("build_algo", "kNN graph construction: 'auto' (exact up to 100k rows, IVF lists beyond), "
                     "'brute_force_knn', 'ivf' (per-query IVF probing) or 'nn_descent' (the IVF graph refined by "
-                    "NN-descent rounds).", TypeConverters.toString)
+                    "NN-descent rounds). Sparse rows (enable_sparse_data_optim): 'auto' / 'brute_force_knn' (the "
+                    "exact CSR search at any row count) or 'rp_nn_descent' (approximate: candidates from a seeded "
+                    "random projection, NN-descent rounds on the CSR rows in the fit's metric).",
+                    TypeConverters.toString)
     build_kwds = _p("build_kwds", "kNN graph options, e.g. {'nlist': ..., 'nprobe': ..., 'probe': 'query' | 'list', "
-                    "'nnd_iters': ...} for build_algo='ivf' / 'nn_descent'.", TypeConverters.identity)
+                    "'nnd_iters': ...} for build_algo='ivf' / 'nn_descent'; {'proj_dim': ..., 'nnd_iters': ..., "
+                    "'a': ..., 'b': ..., 'R': ...} (and 'nlist' / 'nprobe' / 'probe' for its dense candidate build) "
+                    "for build_algo='rp_nn_descent'.", TypeConverters.identity)
 
     def __init__(self) -> None:
         super().__init__()
