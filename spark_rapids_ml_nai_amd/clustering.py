@@ -5,6 +5,13 @@ KMeans param mapping: ``initMode -> init`` ("k-means||" -> scalable-k-means++), 
 n_clusters``, ``maxIter -> max_iter``, ``seed -> random_state``, ``tol -> tol`` (0 mapped to
 float32 tiny with a warning), ``distanceMeasure``/``weightCol`` unsupported, ``initSteps``,
 ``solver``, ``maxBlockSizeInMB`` ignored. Default seed: a stable 31-bit hash of the class name.
+
+Sparse features (``enable_sparse_data_optim=True``, or ``None`` and a first row that is a
+``SparseVector``): the vector column stays CSR from the frame to the device, the fit is
+``models.kmeans.kmeans_fit_csr`` (CSR nearest-centre search and CSR cluster sums, no centring, no
+densified X) and ``transform`` labels sparse-vector partitions with the CSR search. The model is
+the dense ``cluster_centers_`` either way. The default is ``False``: sparse vectors are densified,
+as before the Param existed. ``distanceMeasure="cosine"`` and ``weightCol`` stay unsupported.
 """
 from __future__ import annotations
 
@@ -20,6 +27,7 @@ from .core.dataframe import DataFrame
 from .core.linalg import as_dense_array
 from .core.params import (
     HasDistanceMeasure,
+    HasEnableSparseDataOptim,
     HasFeaturesCol,
     HasFeaturesCols,
     HasIDCol,
@@ -83,7 +91,8 @@ class KMeansClass(_BackendClass):
 
 
 class _KMeansParams(_BackendParams, HasFeaturesCol, HasFeaturesCols, HasPredictionCol, HasMaxIter, HasTol,
-                    HasSeed, HasDistanceMeasure, HasWeightCol, HasSolver, HasMaxBlockSizeInMB, _FeaturesColMixin):
+                    HasSeed, HasDistanceMeasure, HasWeightCol, HasSolver, HasMaxBlockSizeInMB, HasEnableSparseDataOptim,
+                    _FeaturesColMixin):
     k = Param(Params._dummy(), "k", "The number of clusters to create. Must be > 1.", typeConverter=TypeConverters.toInt)
     initMode = Param(Params._dummy(), "initMode", 'The initialization algorithm: "random" or "k-means||".',
                      typeConverter=TypeConverters.toString)
@@ -95,6 +104,9 @@ class _KMeansParams(_BackendParams, HasFeaturesCol, HasFeaturesCols, HasPredicti
         self._setDefault(k=2, initMode="k-means||", initSteps=2, tol=1e-4, maxIter=20, distanceMeasure="euclidean",
                          solver="auto", maxBlockSizeInMB=0.0, featuresCol="features", predictionCol="prediction",
                          seed=_stable_seed(type(self).__name__))
+        # None (first row decides) would re-route existing fits of sparse vector columns to the CSR
+        # kernels and change their last bits: sparse input is opt-in, as for UMAP
+        self._setDefault(enable_sparse_data_optim=False)
 
     def getK(self) -> int:
         return self.getOrDefault("k")
@@ -112,10 +124,13 @@ class KMeans(KMeansClass, _Estimator, _KMeansParams):
     @keyword_only
     def __init__(self, *, featuresCol: Union[str, List[str]] = "features", predictionCol: str = "prediction",
                  k: int = 2, initMode: str = "k-means||", tol: float = 0.0001, maxIter: int = 20,
-                 seed: Optional[int] = None, num_workers: Optional[int] = None, verbose: Union[int, bool] = False,
-                 **kwargs: Any) -> None:
+                 seed: Optional[int] = None, enable_sparse_data_optim: Optional[bool] = False,
+                 num_workers: Optional[int] = None, verbose: Union[int, bool] = False, **kwargs: Any) -> None:
         super().__init__()
         self._set_params(**self._input_kwargs)
+
+    def _supports_sparse(self) -> bool:
+        return True
 
     def setK(self, value: int) -> "KMeans":
         return self._set_params(k=value)
@@ -141,9 +156,14 @@ class KMeans(KMeansClass, _Estimator, _KMeansParams):
         init_steps = self.getOrDefault("initSteps")
 
         def _fit(inp: FitInput, ctx: WorkerContext, params: Dict[str, Any]) -> Dict[str, Any]:
-            from .models.kmeans import kmeans_fit
+            from .core.base import CSR
+            from .models.kmeans import kmeans_fit, kmeans_fit_csr
 
             p = params["cuml_init"]
+            if isinstance(inp.X, CSR):  # a sparse vector column kept CSR (enable_sparse_data_optim)
+                return kmeans_fit_csr(inp.X, inp.desc, ctx, int(p["n_clusters"]), int(p["max_iter"]), float(p["tol"]),
+                                      int(p["random_state"]), p["init"], float(p.get("oversampling_factor", 2.0)),
+                                      init_steps)
             return kmeans_fit(inp.X, inp.desc, ctx, int(p["n_clusters"]), int(p["max_iter"]), float(p["tol"]),
                               int(p["random_state"]), p["init"], float(p.get("oversampling_factor", 2.0)), init_steps)
 
@@ -184,6 +204,11 @@ class KMeansModel(KMeansClass, _ModelWithPredictionCol, _KMeansParams):
 
         return to_spark_kmeans_model(self)
 
+    def _transform_supports_sparse(self) -> bool:
+        # sparse-vector partitions stay CSR unless the Param says densify (False, the default: a
+        # transform that densified before this route existed keeps doing so)
+        return self.getOrDefault("enable_sparse_data_optim") is not False
+
     def _get_transform_func(self, dataset: DataFrame) -> Tuple[Callable, Callable]:
         C = np.asarray(self.cluster_centers_, dtype=np.float32)
         pred_col = self.getPredictionCol()
@@ -192,9 +217,14 @@ class KMeansModel(KMeansClass, _ModelWithPredictionCol, _KMeansParams):
             return torch.from_numpy(C).to(ctx.device)
 
         def predict(Cd: torch.Tensor, X: Any, ctx: WorkerContext) -> Dict[str, np.ndarray]:
-            from .core.base import to_device
-            from .models.kmeans import kmeans_predict, kmeans_predict_streamed, predict_streams
+            import scipy.sparse as sp
 
+            from .core.base import to_device
+            from .models.kmeans import kmeans_predict, kmeans_predict_csr, kmeans_predict_streamed, predict_streams
+
+            if sp.issparse(X):  # a sparse-vector partition: the CSR search, nothing densified
+                Xd = to_device(X, ctx.device, torch.float32)
+                return {pred_col: kmeans_predict_csr(Xd, Cd).cpu().numpy().astype(np.int32)}
             if ctx.device.type == "cuda" and predict_streams(X, Cd.shape[0]):  # H2D under the search
                 return {pred_col: kmeans_predict_streamed(X, Cd, ctx.device).cpu().numpy().astype(np.int32)}
             Xd = to_device(X, ctx.device, torch.float32)

@@ -31,8 +31,13 @@ from ..utils.determinism import deterministic
 from ..parallel.context import PartitionDescriptor, WorkerContext
 
 
-def _global_rows(X: torch.Tensor, desc: PartitionDescriptor, ctx: WorkerContext, idx: np.ndarray) -> torch.Tensor:
-    """Gather rows with the given global indices onto every rank (owner contributes, all-reduce)."""
+def _is_csr(X: Any) -> bool:
+    return hasattr(X, "indptr") and hasattr(X, "indices")
+
+
+def _global_rows(X: Any, desc: PartitionDescriptor, ctx: WorkerContext, idx: np.ndarray) -> torch.Tensor:
+    """Gather rows with the given global indices onto every rank (owner contributes, all-reduce).
+    ``X`` may be a device ``CSR``: the picked rows are densified."""
     n = X.shape[1]
     start = sum(s for r, s in desc.parts_rank_size if r < desc.rank)
     stop = start + X.shape[0]
@@ -40,7 +45,8 @@ def _global_rows(X: torch.Tensor, desc: PartitionDescriptor, ctx: WorkerContext,
     mine = np.nonzero((idx >= start) & (idx < stop))[0]
     if len(mine):
         rows = torch.from_numpy(idx[mine] - start).to(X.device)
-        out[torch.from_numpy(mine).to(X.device)] = X.index_select(0, rows).double()
+        sel = ops.csr_gather_dense(X, rows) if _is_csr(X) else X.index_select(0, rows)
+        out[torch.from_numpy(mine).to(X.device)] = sel.double()
     ctx.comm.allreduce(out)
     return out
 
@@ -61,7 +67,7 @@ def sample_distinct(m: int, k: int, seed: int) -> np.ndarray:
     return got
 
 
-def init_random(X: torch.Tensor, desc: PartitionDescriptor, ctx: WorkerContext, k: int, seed: int) -> torch.Tensor:
+def init_random(X: Any, desc: PartitionDescriptor, ctx: WorkerContext, k: int, seed: int) -> torch.Tensor:
     idx = sample_distinct(desc.m, k, seed)
     C = _global_rows(X, desc, ctx, idx)
     if C.shape[0] < k:  # fewer rows than clusters: duplicate
@@ -91,7 +97,7 @@ def _weighted_lloyd(P: torch.Tensor, w: torch.Tensor, C: torch.Tensor, iters: in
     return C
 
 
-def init_kmeans_parallel(X: torch.Tensor, xnorm: torch.Tensor, desc: PartitionDescriptor, ctx: WorkerContext,
+def init_kmeans_parallel(X: Any, xnorm: Optional[torch.Tensor], desc: PartitionDescriptor, ctx: WorkerContext,
                          k: int, seed: int, oversampling: float = 2.0, steps: int = 2,
                          XP: Optional[torch.Tensor] = None, trials: int = 1, mu: Optional[torch.Tensor] = None,
                          xnorm_split: Optional[torch.Tensor] = None, F16: Any = None) -> torch.Tensor:
@@ -106,11 +112,16 @@ def init_kmeans_parallel(X: torch.Tensor, xnorm: torch.Tensor, desc: PartitionDe
     relative distance error; half the MFMA work of the exact Lloyd passes), or — ``F16`` given
     (``ops.F16Planes``) — the Lloyd loop's fp16 filter pass with radius 0 (its own arg-min, ~1e-3
     relative distance error at worst; only exact ties re-searched): near-equidistant random
-    candidates would otherwise send most rows to the exact re-search."""
+    candidates would otherwise send most rows to the exact re-search.
+    ``X`` may be a device ``CSR`` (``kmeans_fit_csr``): the distance passes are
+    ``ops.csr_nearest_centroid``, the picked rows are densified, the draws are the dense path's."""
     dev = X.device
     m = X.shape[0]
+    csr = _is_csr(X)
 
     def nearest(C: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if csr:
+            return ops.csr_nearest_centroid(X, C)
         if F16 is not None:  # D^2 sampling / weights: the filter's own arg-min, no re-search
             return ops.nearest_centroid_f16(F16, C.float(), approx=True)
         if XP is not None:  # sampling / weighting only need approximate distances
@@ -142,7 +153,7 @@ def init_kmeans_parallel(X: torch.Tensor, xnorm: torch.Tensor, desc: PartitionDe
         ctx.comm.allreduce(phi)
         p = (ell * best_d2.double() / phi.clamp_min(1e-300)).clamp_max(1.0)
         pick = torch.rand(X.shape[0], generator=gen, device=dev, dtype=torch.float64) < p
-        local = X[pick].double()
+        local = (ops.csr_gather_dense(X, torch.nonzero(pick).view(-1)) if csr else X[pick]).double()
         parts = ctx.comm.allgatherv(local)
         new = torch.cat([q.to(dev) for q in parts], 0)
         if new.shape[0] == 0:
@@ -422,6 +433,74 @@ def kmeans_fit(X: torch.Tensor, desc: PartitionDescriptor, ctx: WorkerContext, k
         "refined_frac": round((ops._CERTIFY_STATS["refined"] - st0["refined"]) /
                               max(1, ops._CERTIFY_STATS["rows"] - st0["rows"]), 4) if certified else None,
     }
+
+
+def kmeans_fit_csr(A: Any, desc: PartitionDescriptor, ctx: WorkerContext, k: int, max_iter: int, tol: float,
+                   seed: int, init: str = "scalable-k-means++", oversampling: float = 2.0,
+                   init_steps: int = 2) -> Dict[str, Any]:
+    """``kmeans_fit`` of a device ``CSR`` (sparse vector columns): the rows are never densified.
+    Seeding is the dense path's (same draws; the distance passes are ``ops.csr_nearest_centroid``,
+    the picked rows are densified: a few k of them). Per Lloyd iteration: the CSR search, the CSR
+    cluster sums into the all-reduce buffer [sums (k n) | counts (k)], ONE all-reduce, the
+    centre update (an empty cluster keeps its centre) and the shift test. Full sums every
+    iteration. The data are NOT centred (it would destroy sparsity): the fp32 search's error is
+    relative to (|x| + |c|)^2, not to the spread about the mean."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    k = int(k)
+    t_start = _now(A.data)
+    if k * n * 8 > ops._CSR_KM_SUMS_BYTES:
+        raise ValueError("sparse KMeans: the %d x %d fp64 cluster sums need %d bytes, more than the %d allowed; "
+                         "reduce k or the number of features" % (k, n, k * n * 8, ops._CSR_KM_SUMS_BYTES))
+    if init in ("scalable-k-means++", "k-means||", "k-means++"):
+        cand = 1 + int(max(1, init_steps) * oversampling * k)
+        if cand * n * 8 > ops._CSR_KM_DENSE_BYTES:
+            raise ValueError("sparse KMeans: k-means|| draws about %d candidate rows, %d bytes densified at %d features, "
+                             "more than the %d allowed; use initMode='random' or a smaller k"
+                             % (cand, cand * n * 8, n, ops._CSR_KM_DENSE_BYTES))
+    ops._csr_km_check(A)
+    t_prep = _now(A.data)
+    if init in ("random",):
+        C = init_random(A, desc, ctx, k, seed)
+    elif init in ("scalable-k-means++", "k-means||", "k-means++"):
+        C = init_kmeans_parallel(A, None, desc, ctx, k, seed, oversampling, init_steps)
+    else:
+        raise ValueError("Unsupported init mode %s" % init)
+    C = C.double()
+    t_init = _now(A.data)
+    tol2 = float(tol) ** 2
+    n_iter = 0
+    buf = torch.empty(k * n + k, dtype=torch.float64, device=A.data.device)
+    ws: Dict[Any, torch.Tensor] = {}  # the search's transposed centre table, allocated once
+    # deterministic sums: max|x| sets their fixed-point scale; the data do not change, one read-back
+    vmax = float(A.data.abs().max().item()) if deterministic() and A.data.numel() else None
+    for it in range(max(0, max_iter)):
+        n_iter = it + 1
+        labels, _ = ops.csr_nearest_centroid(A, C, ws=ws)
+        _, counts = ops.csr_cluster_sums(A, labels, k, out=buf[: k * n].view(k, n), vmax=vmax)
+        buf[k * n:] = counts.double()
+        ctx.comm.allreduce(buf)
+        sums = buf[: k * n].view(k, n)
+        counts = buf[k * n:]
+        newC = torch.where(counts.view(-1, 1) > 0, sums / counts.clamp_min(1.0).view(-1, 1), C)
+        shift = float(((newC - C) ** 2).sum(1).max().item())
+        C = newC
+        if shift <= tol2:
+            break
+    t_end = _now(A.data)
+    return {
+        "cluster_centers_": C.cpu().numpy(),
+        "n_cols": int(n),
+        "dtype": "float32" if A.data.dtype == torch.float32 else "float64",
+        "n_iter": n_iter,
+        "delta_iters": 0,
+        "phase_s": [round(t_prep - t_start, 4), round(t_init - t_prep, 4), round(t_end - t_init, 4)],
+        "refined_frac": None,
+    }
+
+
+def kmeans_predict_csr(A: Any, C: torch.Tensor) -> torch.Tensor:
+    """Labels of the CSR rows ``A`` under the dense centres ``C`` (``ops.csr_nearest_centroid``)."""
+    return ops.csr_nearest_centroid(A, C)[0]
 
 
 def kmeans_predict(X: torch.Tensor, C: torch.Tensor) -> torch.Tensor:

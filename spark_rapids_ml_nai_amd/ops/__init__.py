@@ -3958,6 +3958,224 @@ def csr_nnd_join(Q_rows: Any, I: Any, pos: torch.Tensor, perm: Optional[torch.Te
 
 
 # ------------------------------------------------------------------------------------------
+# KMeans on CSR rows against dense centres (csrc/csr_kmeans.hip)
+# dispatch constants of csrc/csr_kmeans.hip (srml_csr_kmeans_config returns the same three)
+CSR_KM_TK = 256             # centres per pass of the search: 64 lanes x 4 accumulators (KM_TK)
+CSR_KM_STAGE = 512          # non-zeros of a row staged in LDS and re-used across centre tiles (KM_STAGE)
+CSR_KM_ROWS = 4             # rows (waves) per block (KM_ROWS)
+_CSR_KM_LAUNCH_ROWS = 1 << 22   # rows of one search launch (16.7M blocks of 4 rows is the grid's limit)
+_CSR_KM_SUMS_BYTES = 16 << 30   # the k x n fp64 cluster-sum buffer a fit may ask for
+_CSR_KM_CT_BYTES = 8 << 30      # the transposed, 64-padded centre table (n x kp) of the search
+_CSR_KM_DENSE_BYTES = 4 << 30   # densified rows (seeding candidates) one gather may ask for
+_CSR_KM_TORCH_ELEMS = 1 << 24   # (rows x centres) keys of one chunk of the torch form
+
+
+def _csr_km_check(A: Any) -> Tuple[int, int]:
+    """The (first, last) offset of the CSR ``A`` after the one-time structural check the KMeans
+    kernels rely on (``csr_prepare``'s): int64 / int32 arrays, monotone row offsets inside the index
+    array, every column index in [0, n), strictly increasing within a row (so no duplicates).
+    ``ValueError`` otherwise, before any launch. ``A.indptr`` may be a slice of a larger matrix's
+    row offsets (a row block with ABSOLUTE offsets is accepted)."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    indptr, indices = A.indptr, A.indices
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise TypeError("CSR kernels need int64 row offsets and int32 column indices")
+    if A.data.dtype not in (torch.float32, torch.float64):
+        raise TypeError("CSR kernels support fp32/fp64 values")
+    if indptr.numel() != m + 1 or indices.numel() != A.data.numel():
+        raise ValueError("inconsistent CSR arrays")
+    done = getattr(A, "_srml_km_checked", None)
+    if done is not None:
+        return done
+    a, b = (int(indptr[0]), int(indptr[-1])) if m else (0, 0)
+    if a < 0 or b > indices.numel() or b < a or (m and bool((indptr[1:] < indptr[:-1]).any())):
+        raise ValueError("CSR row offsets are not a monotone sequence inside the index array")
+    idx = indices[a:b]
+    if idx.numel():
+        if bool(((idx < 0) | (idx >= n)).any()):
+            raise ValueError("CSR column index out of range [0, %d)" % n)
+        rising = idx[1:] > idx[:-1]
+        starts = indptr[1:-1] - a
+        starts = starts[(starts > 0) & (starts < idx.numel())]
+        rising[starts - 1] = True  # a row's first index follows another row's last: no order between them
+        if not bool(rising.all()):
+            raise ValueError("CSR column indices must be strictly increasing within each row")
+    try:
+        A._srml_km_checked = (a, b)
+    except AttributeError:
+        pass
+    return a, b
+
+
+def _csr_km_rows(A: Any, a: int, b: int) -> torch.Tensor:
+    """Row number of every non-zero a .. b of the block."""
+    m = int(A.shape[0])
+    return torch.repeat_interleave(torch.arange(m, device=A.indptr.device), A.indptr[1:] - A.indptr[:-1])
+
+
+def csr_nearest_centroid(A: Any, C: torch.Tensor,
+                         ws: Optional[Dict[Any, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(labels int32 [m], squared distances [m]) of the CSR rows ``A`` against the dense centres ``C``
+    (k, n), in the values' precision (fp32 or fp64): key_j = |x|^2 + |c_j|^2 - 2 x.c_j clamped at 0,
+    the lowest centre index on bit-equal keys; an empty row gets arg-min |c|^2. The centres are
+    rounded to the values' dtype first; |x|^2 and |c|^2 are roundings of fp64 sums.
+
+    Device: ``srml_csr_nearest_{f32,f64}`` on the transposed, 64-padded centres
+    (``srml_csr_centres_transpose_*`` writes the whole n x kp table; ``ws``, a dict the caller keeps
+    across calls, holds that table so that a fit allocates it once; a table past
+    ``_CSR_KM_CT_BYTES`` or the free device memory raises ``ValueError``), at most
+    ``_CSR_KM_LAUNCH_ROWS`` rows per launch (rows are independent: any split gives the same bits).
+    CPU tensors: a torch sparse product per row chunk. Indices are validated before any launch
+    (``ValueError`` for unsorted, duplicated or out-of-range ones)."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    if C.ndim != 2 or C.shape[1] != n or C.shape[0] < 1:
+        raise ValueError("csr_nearest_centroid: centres %s do not match %d features" % (tuple(C.shape), n))
+    a, b = _csr_km_check(A)
+    T = A.data.dtype
+    dev = A.data.device
+    k = int(C.shape[0])
+    Cd = C.to(device=dev, dtype=T)
+    cn = (Cd.double() * Cd.double()).sum(1).to(T)
+    labels = torch.empty(m, dtype=torch.int32, device=dev)
+    d2 = torch.empty(m, dtype=T, device=dev)
+    if m == 0:
+        return labels, d2
+    if not A.data.is_cuda:
+        rows = _csr_km_rows(A, a, b)
+        vals = A.data[a:b]
+        xn = zeros(m, dtype=torch.float64).index_add_(0, rows, vals.double() * vals.double()).to(T)
+        Ct = _c(Cd.t())
+        order = torch.arange(k, dtype=torch.int64)
+        step = max(1, _CSR_KM_TORCH_ELEMS // k)
+        for r0 in range(0, m, step):
+            r1 = min(m, r0 + step)
+            ip = A.indptr[r0: r1 + 1]
+            p0, p1 = int(ip[0]), int(ip[-1])
+            S = torch.sparse_csr_tensor(ip - p0, A.indices[p0:p1].long(), A.data[p0:p1], (r1 - r0, n)) @ Ct
+            key = ((xn[r0:r1].view(-1, 1) + cn.view(1, -1)) - 2 * S).clamp_min(0)
+            best = key.min(1).values
+            labels[r0:r1] = torch.where(key == best.view(-1, 1), order.view(1, -1),
+                                        torch.full((1, 1), k, dtype=torch.int64)).min(1).values.to(torch.int32)
+            d2[r0:r1] = best
+        return labels, d2
+    kp = (k + 63) // 64 * 64
+    key = ("CT", n, kp, T, dev)
+    CT = ws.get(key) if ws is not None else None
+    if CT is None:
+        need = n * kp * A.data.element_size()
+        limit = min(_CSR_KM_CT_BYTES, int(torch.cuda.mem_get_info(dev)[0]))
+        if need > limit:
+            raise ValueError("csr_nearest_centroid: the %d x %d transposed centre table (k = %d padded to %d) needs %d "
+                             "bytes, more than the %d available; reduce k or the number of features"
+                             % (n, kp, k, kp, need, limit))
+        CT = torch.empty((n, kp), dtype=T, device=dev)
+        if ws is not None:
+            ws[key] = CT
+    indptr, st = _c(A.indptr), native.stream(dev)
+    native.call("srml_csr_centres_transpose_" + _sfx(A), _c(Cd).data_ptr(), k, n, kp, CT.data_ptr(), st)
+    cnp = torch.full((kp,), float("inf"), dtype=T, device=dev)
+    cnp[:k] = cn
+    step = max(CSR_KM_ROWS, int(_CSR_KM_LAUNCH_ROWS) // CSR_KM_ROWS * CSR_KM_ROWS)
+    for r0 in range(0, m, step):
+        r = min(step, m - r0)
+        rc = native.call_status("srml_csr_nearest_" + _sfx(A), indptr[r0:].data_ptr(), A.indices.data_ptr(),
+                                A.data.data_ptr(), r, CT.data_ptr(), cnp.data_ptr(), k, kp, labels[r0:].data_ptr(),
+                                d2[r0:].data_ptr(), st)
+        if rc < 0:
+            raise ValueError("srml_csr_nearest refused the launch (status %d: -1 grid overflow, -2 centre count / "
+                             "padding) for %d rows, k=%d, kp=%d" % (rc, r, k, kp))
+        if rc != 0:
+            raise RuntimeError("srml_csr_nearest launch failed with HIP status %d" % rc)
+    return labels, d2
+
+
+def csr_fixed_scale(rows: int, vmax: float) -> float:
+    """The power of two 2^s by which the deterministic cluster sums scale a value before rounding it
+    to an integer: with 2^e >= rows * vmax (e from ``frexp``), s = 62 - e keeps any sum of ``rows``
+    such integers inside i64. Values down to 2^-39 of rows * vmax convert exactly (fp32 values)."""
+    bound = float(rows) * float(vmax)
+    if not math.isfinite(bound):
+        raise ValueError("deterministic cluster sums need finite values (rows * max|value| = %r)" % bound)
+    e = math.frexp(bound)[1] if bound > 0 else 0
+    return math.ldexp(1.0, max(-1000, min(1000, 62 - e)))
+
+
+def csr_cluster_sums(A: Any, labels: torch.Tensor, k: int, out: Optional[torch.Tensor] = None,
+                     vmax: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(sums fp64 [k, n], counts int64 [k]) of the CSR rows ``A`` grouped by ``labels`` (rows with a
+    label outside [0, k) are ignored). Device: ``srml_csr_cluster_sums_{f32,f64}``, one fp64 atomic
+    per non-zero, counts from ``label_counts``. Deterministic mode: the values are scaled by
+    ``csr_fixed_scale(m, max|value|)``, rounded to integers and added with i64 atomics — integer
+    addition is exact in any order, so the result repeats bit for bit and does not depend on the
+    order of the rows — then converted to fp64 once. ``out`` (fp64 [k, n], contiguous, on the
+    values' device): the sums are written there (zeroed here). ``vmax``: max|value| of ``A`` when the
+    caller already has it (a fit reads it back once, not per iteration). A k x n buffer past ``_CSR_KM_SUMS_BYTES`` (or
+    the device's free memory) raises ``ValueError``."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    k = int(k)
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    if labels.numel() != m:
+        raise ValueError("csr_cluster_sums: %d labels for %d rows" % (labels.numel(), m))
+    need = k * n * 8
+    limit = _CSR_KM_SUMS_BYTES
+    if out is None and A.data.is_cuda and need <= limit:
+        limit = min(limit, int(torch.cuda.mem_get_info(dev)[0]))
+    if need > limit and out is None:
+        raise ValueError("csr_cluster_sums: the %d x %d fp64 cluster sums need %d bytes, more than the %d available; "
+                         "reduce k or the number of features" % (k, n, need, limit))
+    lab = _c(labels.to(device=dev, dtype=torch.int32))
+    counts = label_counts(lab, k)
+    if out is not None:
+        if out.shape != (k, n) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+            raise ValueError("csr_cluster_sums: out must be a contiguous fp64 (%d, %d) tensor on %s" % (k, n, dev))
+        sums = zero_(out)
+    else:
+        sums = zeros((k, n), dtype=torch.float64, device=dev)
+    if m == 0 or b == a or k == 0 or n == 0:
+        return sums, counts
+    scale = 0.0
+    if deterministic():
+        scale = csr_fixed_scale(m, float(A.data[a:b].abs().max().item()) if vmax is None else float(vmax))
+    if not A.data.is_cuda:
+        rl = lab.long()[_csr_km_rows(A, a, b)]
+        ok = (rl >= 0) & (rl < k)
+        cell = rl[ok] * n + A.indices[a:b].long()[ok]
+        v = A.data[a:b].double()[ok]
+        if scale:
+            acc = torch.zeros(k * n, dtype=torch.int64).index_add_(0, cell, torch.round(v * scale).long())
+            sums.copy_((acc.double() * (1.0 / scale)).view(k, n))
+        else:
+            sums.view(-1).index_add_(0, cell, v)
+        return sums, counts
+    native.call("srml_csr_cluster_sums_" + _sfx(A), _c(A.indptr).data_ptr(), A.indices.data_ptr(), A.data.data_ptr(),
+                m, n, b - a, lab.data_ptr(), k, scale, sums.data_ptr(), native.stream(dev))
+    if scale:
+        native.call("srml_csr_cluster_sums_finish", sums.data_ptr(), k * n, 1.0 / scale, native.stream(dev))
+    return sums, counts
+
+
+def csr_gather_dense(A: Any, rows: torch.Tensor) -> torch.Tensor:
+    """The selected rows of the CSR ``A`` as a dense (len(rows), n) matrix of the values' dtype (the
+    KMeans seeding's candidate rows). More than ``_CSR_KM_DENSE_BYTES`` raises ``ValueError``."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    _csr_km_check(A)
+    rows = rows.to(device=A.indptr.device, dtype=torch.int64).view(-1)
+    need = int(rows.numel()) * n * A.data.element_size()
+    if need > _CSR_KM_DENSE_BYTES:
+        raise ValueError("csr_gather_dense: %d rows x %d features need %d bytes densified, more than the %d allowed"
+                         % (rows.numel(), n, need, _CSR_KM_DENSE_BYTES))
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= m):
+        raise ValueError("csr_gather_dense: row outside [0, %d)" % m)
+    out = zeros((int(rows.numel()), n), dtype=A.data.dtype, device=A.data.device)
+    if rows.numel():
+        starts = A.indptr[rows]
+        seg, pos = _csr_segments(starts, A.indptr[rows + 1] - starts)
+        out[seg, A.indices[pos].long()] = A.data[pos]
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # Logistic loss + gradient accumulation for the on-device quasi-Newton driver (models/qn.py)
 def _is_csr(X) -> bool:
     return hasattr(X, "indptr") and hasattr(X, "indices")

@@ -217,6 +217,16 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_csr_nnd_config": (_I,),
     "srml_csr_nnd_join_f32": (_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                               _P),
+    # KMeans on CSR rows: (row offsets, indices, values, rows), then CT, centre norms, k, kp, labels, distances /
+    # n, nnz, labels, k, fixed-point scale (0: fp64 atomics), sums
+    "srml_csr_kmeans_config": (_I,),
+    "srml_csr_centres_transpose_f32": (_P, _I, _I, _I, _P, _P),
+    "srml_csr_centres_transpose_f64": (_P, _I, _I, _I, _P, _P),
+    "srml_csr_nearest_f32": (_P, _P, _P, _L, _P, _P, _I, _I, _P, _P, _P),
+    "srml_csr_nearest_f64": (_P, _P, _P, _L, _P, _P, _I, _I, _P, _P, _P),
+    "srml_csr_cluster_sums_f32": (_P, _P, _P, _L, _I, _L, _P, _I, _D, _P, _P),
+    "srml_csr_cluster_sums_f64": (_P, _P, _P, _L, _I, _L, _P, _I, _D, _P, _P),
+    "srml_csr_cluster_sums_finish": (_P, _L, _D, _P),
     "srml_confusion_counts": (_P, _I, _P, _I, _L, _I, _P, _P),
     "srml_logloss_sum": (_P, _I, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_reg_moments": (_P, _I, _P, _I, _L, _P, _P),

@@ -6,7 +6,9 @@ or the Spark conf ``spark.rocm.ml.deterministic=true`` forwarded to the workers 
 switches the affected kernels to fixed-order variants:
 
 * KMeans cluster sums -> label-sorted segment sums, one block per (cluster, column chunk), no
-  atomics (``srml_kmeans_segment_sums_*``);
+  atomics (``srml_kmeans_segment_sums_*``); on CSR rows (``ops.csr_cluster_sums``) exact i64
+  fixed-point integers added with integer atomics and converted to fp64 once, which also makes the
+  sums independent of the row order;
 * Gram / covariance (PCA, LinearRegression normal equations) -> each row chunk stores its
   partial tiles into a workspace (<= 64 chunks, <= 1 GB) folded in chunk order, instead of
   fp64 atomics (same fp32-per-chunk / fp64-across-chunk precision);
