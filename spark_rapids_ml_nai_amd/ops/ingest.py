@@ -16,6 +16,8 @@ from typing import Any, Iterator, Optional
 import numpy as np
 import torch
 
+from . import native
+
 _CHUNK_BYTES = 64 << 20
 _DIRECT_BYTES = 8 << 20
 _staging: dict = {}
@@ -99,6 +101,23 @@ def _thread_pool() -> Any:
     return _pool
 
 
+def _register_all(blocks: list) -> bool:
+    """Page-lock every block in place. Where the runtime refuses (a virtual machine that cannot
+    register host pointers), the blocks registered so far are released, a warning says so and the
+    caller takes the staged ring: the refusal never stays behind as the runtime's last error."""
+    done = []
+    for b in blocks:
+        rc = native.call_status("srml_host_register", b.ctypes.data, b.nbytes)
+        if rc != 0:
+            for d in done:
+                native.call_status("srml_host_unregister", d.ctypes.data)
+            warnings.warn("hipHostRegister failed with HIP status %d: ingest mode 'register' is not available "
+                          "here, using the staged pinned ring" % rc)
+            return False
+        done.append(b)
+    return True
+
+
 def parts_to_device(parts: Any, device: torch.device, dtype: Optional[torch.dtype] = None,
                     mode: Optional[str] = None) -> torch.Tensor:
     """Row blocks (list of (rows_i, n) arrays, or ``ChunkedRows``) -> one (sum rows_i, n) device
@@ -107,7 +126,8 @@ def parts_to_device(parts: Any, device: torch.device, dtype: Optional[torch.dtyp
     ``staged`` (default): a ring of pinned buffers; each is filled by ``SRML_INGEST_THREADS``
     threads (numpy copies release the GIL; the element-type cast, if any, happens in the same
     copy) and DMA'd on the high-priority copy stream while the next one fills. ``register``: each
-    block is page-locked in place (hipHostRegister), DMA'd directly and unregistered. The compute
+    block is page-locked in place (hipHostRegister), DMA'd directly and unregistered; where the
+    runtime cannot register host memory the call warns and takes the staged ring. The compute
     stream waits for the last copy on the device; the host never blocks on the transfer except to
     recycle a ring slot."""
     blocks = list(getattr(parts, "parts", parts))
@@ -127,21 +147,17 @@ def parts_to_device(parts: Any, device: torch.device, dtype: Optional[torch.dtyp
     cs = copy_stream(device)
     cs.wait_stream(cur)
     out.record_stream(cs)
-    if mode == "register" and all(b.dtype == np_dt for b in blocks):
-        cudart = torch.cuda.cudart()
-        regs = []
+    if mode == "register" and all(b.dtype == np_dt for b in blocks) and _register_all(blocks):
         r0 = 0
         with torch.cuda.stream(cs):
             for b in blocks:
-                cudart.cudaHostRegister(b.ctypes.data, b.nbytes, 0)
-                regs.append(b)
                 with warnings.catch_warnings():
                     warnings.simplefilter("ignore", UserWarning)
                     out[r0: r0 + b.shape[0]].copy_(torch.from_numpy(b), non_blocking=True)
                 r0 += b.shape[0]
         cs.synchronize()  # blocks must stay registered until their DMA has landed
-        for b in regs:
-            cudart.cudaHostUnregister(b.ctypes.data)
+        for b in blocks:
+            native.call("srml_host_unregister", b.ctypes.data)
         cur.wait_stream(cs)
         return out
     for _ in _staged_fill(blocks, out, device, cs):

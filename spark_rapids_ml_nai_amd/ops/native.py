@@ -235,6 +235,8 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_memcpy_h2d_async": (_P, _P, _L, _P),
     "srml_memcpy_d2h_sync": (_P, _P, _L, _P),
     "srml_memset_async": (_P, _I, _L, _P),
+    "srml_host_register": (_P, _L),
+    "srml_host_unregister": (_P,),
     "srml_rf_predict_nodes2": (_P, _L, _L, _I, _P, _P, _I, _P, _I, _P, _P, _P),
     "srml_rf_predict": (_P, _L, _L, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P),
     "srml_rf_left_totals": (_P, _I, _L, _I, _I, _I, _P, _P, _P),
