@@ -265,7 +265,9 @@ class _DBSCANParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatur
     metric = Param(Params._dummy(), "metric", "The metric to use when calculating distances between points "
                    "('euclidean' or 'cosine'; 'precomputed' is not supported).", typeConverter=TypeConverters.toString)
     algorithm = Param(Params._dummy(), "algorithm", "The algorithm to be used by for nearest neighbor computations "
-                      "('brute' or 'rbc'; both run the fused brute-force tile sweep).",
+                      "('brute': the fused tile sweep over every tile pair; 'rbc': rows grouped into balls by "
+                      "nearest landmark, the same sweep over only the tile pairs whose balls can hold a "
+                      "neighbour, with the labels of 'brute').",
                       typeConverter=TypeConverters.toString)
     max_mbytes_per_batch = Param(Params._dummy(), "max_mbytes_per_batch",
                                  "Accepted for compatibility; the tiled kernels never materialise the N x N "
@@ -320,17 +322,19 @@ class _DBSCANParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatur
         return self._set_params(idCol=value)
 
 
-def _dbscan_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarray, np.ndarray]:
+def _dbscan_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarray, np.ndarray, Tuple[int, int]]:
     from .core.base import to_device
     from .models.dbscan import dbscan_fit_predict
 
-    X, eps, min_samples, metric = payload
+    X, eps, min_samples, metric, algorithm = payload
     if ctx.world_size > 1:  # an empty shard learns the feature count from the other ranks
         nt = torch.tensor([float(X.shape[1] if X.ndim == 2 else 0)], dtype=torch.float64, device=ctx.device)
         ctx.comm.allreduce(nt, op="max")
         X = np.asarray(X, np.float32).reshape(-1, int(nt.item())) if X.size == 0 else X
     Xd = to_device(X, ctx.device, torch.float32)
-    return dbscan_fit_predict(Xd, ctx, eps, min_samples, metric)
+    stats: Dict[str, Any] = {}
+    labels, core = dbscan_fit_predict(Xd, ctx, eps, min_samples, metric, algorithm, stats)
+    return labels, core, stats["tile_pairs"]
 
 
 def _spark_dbscan_task(ctx: WorkerContext, table: Any, extra: Tuple[Any, ...]) -> Any:
@@ -343,14 +347,14 @@ def _spark_dbscan_task(ctx: WorkerContext, table: Any, extra: Tuple[Any, ...]) -
     from .core.base import _dense_from_df
     from .core.dataframe import DataFrame as _DF
 
-    col, cols, id_col, pred_col, eps, min_samples, metric = extra
+    col, cols, id_col, pred_col, eps, min_samples, metric, algorithm = extra
     if table is not None and table.num_rows:
         part = _DF([table])
         X = _dense_from_df(part, col, cols, np.float32)
         ids = np.asarray(part.to_numpy(id_col)).astype(np.int64)
     else:  # an empty rank still joins every collective (the worker agrees on n)
         X, ids = np.zeros((0, 0), np.float32), np.zeros(0, np.int64)
-    labels, _core = _dbscan_worker(ctx, (X, eps, min_samples, metric))
+    labels, _core, _pairs = _dbscan_worker(ctx, (X, eps, min_samples, metric, algorithm))
     yield pa.RecordBatch.from_arrays([pa.array(ids), pa.array(np.asarray(labels).astype(np.int32))],
                                      names=[id_col, pred_col])
 
@@ -401,6 +405,7 @@ class DBSCANModel(DBSCANClass, _ModelWithPredictionCol, _DBSCANParams):
         self.dtype = dtype
         self.verbose = verbose
         self.core_sample_indices_: Optional[np.ndarray] = None
+        self._tile_pairs_: Optional[Tuple[int, int]] = None
 
     def _get_transform_func(self, dataset: DataFrame) -> Tuple[Callable, Callable]:
         raise NotImplementedError("DBSCANModel clusters the whole dataset in transform()")
@@ -428,7 +433,8 @@ class DBSCANModel(DBSCANClass, _ModelWithPredictionCol, _DBSCANParams):
         pred = self.getPredictionCol()
         schema = StructType([StructField(id_col, LongType()), StructField(pred, IntegerType())])
         labels = spark_barrier_job(job_in, _spark_dbscan_task, (col, cols, id_col, pred, self.getEps(),
-                                                                self.getMinSamples(), self.getMetric()), schema)
+                                                                self.getMinSamples(), self.getMetric(),
+                                                                self.getAlgorithm()), schema)
         return df_withid.join(labels, on=id_col)
 
     def _features_all(self, df: DataFrame) -> np.ndarray:
@@ -448,15 +454,16 @@ class DBSCANModel(DBSCANClass, _ModelWithPredictionCol, _DBSCANParams):
             # index into this rank's frame
             parts = df.partitions
             X = self._features_all(df) if df.count() else np.zeros((0, 0), np.float32)
-            payloads = [(X, self.getEps(), self.getMinSamples(), self.getMetric())]
+            payloads = [(X, self.getEps(), self.getMinSamples(), self.getMetric(), self.getAlgorithm())]
         else:
             nw = max(1, self.num_workers)
             parts = df.repartition(nw).partitions if df.getNumPartitions() != nw else df.partitions
-            payloads = [(self._features_all(DataFrame([p])), self.getEps(), self.getMinSamples(), self.getMetric())
-                        for p in parts]
+            payloads = [(self._features_all(DataFrame([p])), self.getEps(), self.getMinSamples(), self.getMetric(),
+                         self.getAlgorithm()) for p in parts]
         res = run_worker_job(_dbscan_worker, payloads)
         labels = np.concatenate([r[0] for r in res]).astype(np.int32)
         core = np.concatenate([r[1] for r in res])
+        self._tile_pairs_ = tuple(res[0][2])  # (visited, total) tile pairs of the sweeps, all ranks together
         if self.getCalcCoreSampleIndices():
             self.core_sample_indices_ = np.nonzero(core)[0]
         out = DataFrame(parts) if len(parts) != df.getNumPartitions() else df

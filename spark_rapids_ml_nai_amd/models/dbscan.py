@@ -10,10 +10,15 @@ the forests are all-gathered and merged on device (every rank ends with identica
 smallest core index of each component), border keys all-reduced with MIN. Labels are numbered
 by ascending root, i.e. in order of each cluster's first core point (sklearn's numbering);
 noise is -1.
+
+``algorithm="rbc"`` (ball cover): the rows are grouped by nearest landmark so that a tile is a compact
+ball, the tile pairs whose balls are further apart than eps (plus the fp32 form's error band) are
+dropped on the device, and the two sweeps run over the surviving list only, each rank on its share of
+that list. Results are indexed by original row id throughout, so the answers are those of brute.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -49,22 +54,84 @@ def _prepare(X: torch.Tensor, eps: float, metric: str) -> Tuple[torch.Tensor, to
     raise ValueError("Unsupported metric %r for DBSCAN" % metric)
 
 
+RBC_MAX_LANDMARKS = 16384
+
+
+def _rbc_order(X: torch.Tensor, xn: torch.Tensor) -> torch.Tensor:
+    """Permutation (position -> row id, int32) that groups the rows by nearest landmark, so that a
+    128-row tile of ``X[perm]`` is a compact ball. Landmarks: L = min(T, 16384) rows at a fixed stride.
+    Neighbouring groups should be neighbours in space too (a tile that straddles two groups far apart is a
+    ball that reaches everything), so the landmarks are ranked first: ceil(sqrt(L)) of them serve as
+    second-level landmarks, and a landmark's rank is its place in the order (nearest second-level
+    landmark, distance to it). The rows are then sorted by the unique keys (landmark rank << 32 | row):
+    the order depends on ``X`` alone, every rank holds the same matrix and gets the same permutation.
+    The grouping only affects how many tile pairs survive the pruning, never the result."""
+    N = X.shape[0]
+    T = (N + ops.DB_TILE - 1) // ops.DB_TILE
+    L = min(T, RBC_MAX_LANDMARKS)
+    lm = X[:: N // L][:L].contiguous()
+    L2 = int(np.ceil(np.sqrt(L)))
+    top, dtop = ops.nearest_centroid(lm, lm[:: L // L2][:L2].contiguous())
+    # a distance >= 0 orders as its bits; the mask keeps a -0.0 out of the high word
+    lkeys = (top.long() << 32) | (dtop.contiguous().view(torch.int32).long() & 0xFFFFFFFF)
+    order = torch.arange(L, dtype=torch.int32, device=X.device)
+    ops.radix_sort_pairs(lkeys, order, 32 + max(1, int(L2).bit_length()))
+    rank = torch.empty(L, dtype=torch.int64, device=X.device)
+    rank[order.long()] = torch.arange(L, dtype=torch.int64, device=X.device)
+    owner, _ = ops.nearest_centroid(X, lm, xnorm=xn)
+    perm = torch.arange(N, dtype=torch.int32, device=X.device)
+    keys = (rank[owner.long()] << 32) | perm.long()
+    ops.radix_sort_pairs(keys, perm, 32 + max(1, int(L).bit_length()))
+    return perm
+
+
+def _rbc_pairs(X: torch.Tensor, xn: torch.Tensor, eps2: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                         torch.Tensor]:
+    """(Xp, xnp, perm, pairs): the rows in ball order and the ascending list of the tile pairs of ``Xp`` that
+    can hold a pair the brute sweep counts (``ops.dbscan_tile_pairs``). ``band`` widens eps2 by the expanded
+    form's own error bound c(n) 2^-24 (2 R)^2, R the largest row norm, so no pair the brute sweep could
+    still count is pruned: the two algorithms return the same labels, not merely both valid ones."""
+    n = X.shape[1]
+    perm = _rbc_order(X, xn)
+    Xp = X[perm.long()].contiguous()
+    xnp = xn[perm.long()].contiguous()
+    band = (1.5 * n + 8.0) * 2.0 ** -24 * 4.0 * float(xn.max().item())
+    centres, radii, cnorm = ops.dbscan_tile_balls(Xp)
+    return Xp, xnp, perm, ops.dbscan_tile_pairs(centres, radii, cnorm, eps2, band)
+
+
 def dbscan_fit_predict(X_local: torch.Tensor, ctx: WorkerContext, eps: float, min_samples: int,
-                       metric: str = "euclidean") -> Tuple[np.ndarray, np.ndarray]:
-    """(labels of this rank's rows, core-sample flags of this rank's rows)."""
+                       metric: str = "euclidean", algorithm: str = "brute",
+                       stats: Optional[Dict[str, Any]] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(labels of this rank's rows, core-sample flags of this rank's rows). ``algorithm="rbc"`` (more than two
+    row tiles): the two sweeps visit only the tile pairs whose balls can hold a neighbour; the answers
+    are those of ``"brute"``. ``stats["tile_pairs"]`` receives (visited, total) tile pairs over all ranks."""
     parts = ctx.comm.allgatherv(X_local.float().contiguous())
     sizes = [p.shape[0] for p in parts]
     start = sum(sizes[: ctx.rank])
     X = torch.cat([p.to(X_local.device) for p in parts], 0).contiguous()
     N = X.shape[0]
     X, xn, eps2 = _prepare(X, eps, metric)
-    t0, t1 = _share(ops.dbscan_num_tiles(N), ctx.rank, ctx.world_size)
-    counts = ops.dbscan_degree(X, xn, eps2, t0, t1)
-    ctx.comm.allreduce(counts)
-    core = (counts >= int(min_samples)).to(torch.uint8)
+    total = ops.dbscan_num_tiles(N)
     parent = torch.arange(N, dtype=torch.int32, device=X.device)
     best = torch.full((N,), -1, dtype=torch.int64, device=X.device)
-    ops.dbscan_link(X, xn, eps2, t0, t1, core, parent, best)
+    if algorithm == "rbc" and N > 2 * ops.DB_TILE:
+        Xp, xnp, perm, pairs = _rbc_pairs(X, xn, eps2)
+        visited = int(pairs.shape[0])
+        l0, l1 = _share(visited, ctx.rank, ctx.world_size)
+        counts = ops.dbscan_degree_list(Xp, xnp, eps2, pairs, l0, l1, perm)
+        ctx.comm.allreduce(counts)
+        core = (counts >= int(min_samples)).to(torch.uint8)
+        ops.dbscan_link_list(Xp, xnp, eps2, pairs, l0, l1, perm, core, parent, best)
+    else:
+        visited = total
+        t0, t1 = _share(total, ctx.rank, ctx.world_size)
+        counts = ops.dbscan_degree(X, xn, eps2, t0, t1)
+        ctx.comm.allreduce(counts)
+        core = (counts >= int(min_samples)).to(torch.uint8)
+        ops.dbscan_link(X, xn, eps2, t0, t1, core, parent, best)
+    if stats is not None:
+        stats["tile_pairs"] = (visited, total)
     if ctx.world_size > 1:
         ctx.comm.allreduce(best, op="min")
         forests = ctx.comm.allgather(parent.view(1, -1))

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Any, Callable, Dict, Iterator, Optional, Tuple
+from typing import Any, Callable, Dict, Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -2826,11 +2826,12 @@ def _tri_decode(t: int) -> Tuple[int, int]:
     return i, t - i * (i + 1) // 2
 
 
-def _db_tiles(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: int) -> Iterator[Any]:
-    """CPU reference: yields (r0, c0, masked squared distances) per tile pair of the range."""
-    N = X.shape[0]
-    for t in range(t0, t1):
-        bi, bj = _tri_decode(t)
+def _db_tiles(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: int,
+              tiles: Optional[Sequence[int]] = None) -> Iterator[Any]:
+    """CPU reference: yields (r0, c0, masked squared distances) per tile pair of the range [t0, t1), or
+    of ``tiles[t0: t1]`` where a list of tile pairs is given."""
+    for t in (range(t0, t1) if tiles is None else tiles[t0: t1]):
+        bi, bj = _tri_decode(int(t))
         r0, c0 = bi * DB_TILE, bj * DB_TILE
         A, B = X[r0: r0 + DB_TILE].float(), X[c0: c0 + DB_TILE].float()
         d = (xnorm[r0: r0 + DB_TILE].float().view(-1, 1) + xnorm[c0: c0 + DB_TILE].float().view(1, -1)
@@ -2840,6 +2841,19 @@ def _db_tiles(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: in
         yield bi == bj, r0, c0, torch.where(d <= eps2, d, torch.full_like(d, float("inf")))
 
 
+def _degree_cpu(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: int, counts: torch.Tensor,
+                tiles: Optional[Sequence[int]] = None, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The degree sweep on the CPU; ``perm`` (position -> id): counts are indexed by id."""
+    for diag, r0, c0, d in _db_tiles(X, xnorm, eps2, t0, t1, tiles):
+        adj = torch.isfinite(d)
+        rid = torch.arange(r0, r0 + d.shape[0], device=d.device) if perm is None else perm[r0: r0 + d.shape[0]]
+        counts.index_add_(0, rid, adj.sum(1).int())
+        if not diag:
+            cid = torch.arange(c0, c0 + d.shape[1], device=d.device) if perm is None else perm[c0: c0 + d.shape[1]]
+            counts.index_add_(0, cid, adj.sum(0).int())
+    return counts
+
+
 def dbscan_degree(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: int,
                   counts: Optional[torch.Tensor] = None) -> torch.Tensor:
     """eps-neighbourhood sizes (self included) accumulated over tile pairs [t0, t1) into int32 counts."""
@@ -2847,12 +2861,7 @@ def dbscan_degree(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1
     if counts is None:
         counts = zeros(N, dtype=torch.int32, device=X.device)
     if not X.is_cuda or X.dtype != torch.float32:
-        for diag, r0, c0, d in _db_tiles(X, xnorm, eps2, t0, t1):
-            adj = torch.isfinite(d)
-            counts[r0: r0 + d.shape[0]] += adj.sum(1).int()
-            if not diag:
-                counts[c0: c0 + d.shape[1]] += adj.sum(0).int()
-        return counts
+        return _degree_cpu(X, xnorm, eps2, t0, t1, counts)
     X = _c(X)
     native.call("srml_dbscan_degree_f32", X.data_ptr(), N, X.shape[1], X.stride(0), _c(xnorm.float()).data_ptr(),
                 float(eps2), int(t0), int(t1), counts.data_ptr(), native.stream(X.device))
@@ -2880,33 +2889,41 @@ def _uf_cpu_merge(parent: torch.Tensor, src: np.ndarray, dst: np.ndarray) -> Non
     parent.copy_(torch.from_numpy(mins[comp].astype(np.int32)))
 
 
+def _link_cpu(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: int, core: torch.Tensor,
+              parent: torch.Tensor, best: torch.Tensor, tiles: Optional[Sequence[int]] = None,
+              perm: Optional[torch.Tensor] = None) -> None:
+    """The link sweep on the CPU; ``perm`` (position -> id): core, parent, best and the keys hold ids."""
+    srcs, dsts = [], []
+    for diag, r0, c0, d in _db_tiles(X, xnorm, eps2, t0, t1, tiles):
+        adj = torch.isfinite(d)
+        rid = torch.arange(r0, r0 + d.shape[0], device=d.device) if perm is None else perm[r0: r0 + d.shape[0]]
+        cid = torch.arange(c0, c0 + d.shape[1], device=d.device) if perm is None else perm[c0: c0 + d.shape[1]]
+        rc = core[rid].bool().view(-1, 1)
+        cc = core[cid].bool().view(1, -1)
+        e = torch.nonzero(adj & rc & cc)
+        srcs.append(rid[e[:, 0]].numpy())
+        dsts.append(cid[e[:, 1]].numpy())
+        ridx = cid.view(1, -1).expand_as(d)
+        cidx = rid.view(-1, 1).expand_as(d)
+        inf = torch.full_like(d, float("inf"))
+        # border row <- core column
+        dr = torch.where(adj & ~rc & cc, d, inf)
+        kr = torch.where(torch.isfinite(dr), _orderable_key(dr, ridx), torch.full_like(ridx, -1))
+        best[rid] = torch.minimum(best[rid], _min_valid(kr, 1))
+        dc = torch.where(adj & rc & ~cc, d, inf)
+        kc = torch.where(torch.isfinite(dc), _orderable_key(dc, cidx), torch.full_like(cidx, -1))
+        best[cid] = torch.minimum(best[cid], _min_valid(kc, 0))
+    if srcs:
+        _uf_cpu_merge(parent, np.concatenate(srcs), np.concatenate(dsts))
+
+
 def dbscan_link(X: torch.Tensor, xnorm: torch.Tensor, eps2: float, t0: int, t1: int, core: torch.Tensor,
                 parent: torch.Tensor, best: torch.Tensor) -> None:
     """Unite core-core eps edges of tile pairs [t0, t1) into ``parent`` (int32 union-find) and keep,
     for every non-core point, the packed key of its nearest core neighbour in ``best`` (int64 MIN)."""
     N = X.shape[0]
     if not X.is_cuda or X.dtype != torch.float32:
-        corb = core.bool()
-        srcs, dsts = [], []
-        for diag, r0, c0, d in _db_tiles(X, xnorm, eps2, t0, t1):
-            adj = torch.isfinite(d)
-            rc = corb[r0: r0 + d.shape[0]].view(-1, 1)
-            cc = corb[c0: c0 + d.shape[1]].view(1, -1)
-            e = torch.nonzero(adj & rc & cc)
-            srcs.append((e[:, 0] + r0).numpy())
-            dsts.append((e[:, 1] + c0).numpy())
-            ridx = torch.arange(c0, c0 + d.shape[1]).view(1, -1).expand_as(d)
-            cidx = torch.arange(r0, r0 + d.shape[0]).view(-1, 1).expand_as(d)
-            inf = torch.full_like(d, float("inf"))
-            # border row <- core column
-            dr = torch.where(adj & ~rc & cc, d, inf)
-            kr = torch.where(torch.isfinite(dr), _orderable_key(dr, ridx), torch.full_like(ridx, -1))
-            best[r0: r0 + d.shape[0]] = torch.minimum(best[r0: r0 + d.shape[0]], _min_valid(kr, 1))
-            dc = torch.where(adj & rc & ~cc, d, inf)
-            kc = torch.where(torch.isfinite(dc), _orderable_key(dc, cidx), torch.full_like(cidx, -1))
-            best[c0: c0 + d.shape[1]] = torch.minimum(best[c0: c0 + d.shape[1]], _min_valid(kc, 0))
-        if srcs:
-            _uf_cpu_merge(parent, np.concatenate(srcs), np.concatenate(dsts))
+        _link_cpu(X, xnorm, eps2, t0, t1, core, parent, best)
         return
     X = _c(X)
     native.call("srml_dbscan_link_f32", X.data_ptr(), N, X.shape[1], X.stride(0), _c(xnorm.float()).data_ptr(),
@@ -2957,6 +2974,114 @@ def uf_compress(parent: torch.Tensor) -> None:
         _uf_cpu_merge(parent, np.zeros(0, np.int64), np.zeros(0, np.int64))
         return
     native.call("srml_uf_compress", parent.data_ptr(), parent.shape[0], native.stream(parent.device))
+
+
+# ---- algorithm="rbc": tile balls, the surviving tile-pair list, the sweeps over that list ----------
+def dbscan_tile_balls(Xp: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(centres fp32 [T, n], radii fp32 [T], ||centre||^2 fp32 [T]) of the T = ceil(N / 128) row tiles of
+    ``Xp``: the centre is the tile's column mean, the radius an upper bound of the largest distance of
+    a tile row from it (direct form, inflated by (1 + (n + 4) 2^-24)). ``srml_dbscan_tile_balls_f32``."""
+    N, n = Xp.shape
+    T = (N + DB_TILE - 1) // DB_TILE
+    if not Xp.is_cuda:
+        X = Xp.float()
+        pad = torch.zeros((T * DB_TILE, n), dtype=torch.float32)
+        pad[:N] = X
+        rows = torch.full((T,), float(DB_TILE))
+        if T:
+            rows[-1] = float(N - (T - 1) * DB_TILE)
+        C = pad.view(T, DB_TILE, n).sum(1) / rows.view(-1, 1)
+        d = ((pad.view(T, DB_TILE, n) - C.view(T, 1, n)) ** 2).sum(2)
+        d[torch.arange(T * DB_TILE).view(T, DB_TILE) >= N] = 0.0
+        r = d.max(1).values.sqrt() * np.float32(1.0 + (n + 4) * 2.0 ** -24)
+        return C, r, (C * C).sum(1)
+    Xp = _c(Xp.float())
+    C = torch.empty((T, n), dtype=torch.float32, device=Xp.device)
+    r = torch.empty(T, dtype=torch.float32, device=Xp.device)
+    cn = torch.empty(T, dtype=torch.float32, device=Xp.device)
+    native.call("srml_dbscan_tile_balls_f32", Xp.data_ptr(), N, n, Xp.stride(0), C.data_ptr(), r.data_ptr(),
+                cn.data_ptr(), native.stream(Xp.device))
+    return C, r, cn
+
+
+def dbscan_tile_pairs(centres: torch.Tensor, radii: torch.Tensor, cnorm: torch.Tensor, eps2: float,
+                      band: float) -> torch.Tensor:
+    """Ascending int64 list of the lower-triangle tile pairs (``_tri_decode`` encoding) whose balls can
+    hold a pair the brute sweep counts within ``eps2``: pair (a, b), b <= a, is kept iff a == b or
+    d2_ab - e_ab <= (r_a + r_b + sqrt(eps2 + band))^2, d2 the fp32 expanded-form centre distance and
+    e_ab = (3 n / 2 + 5) 2^-24 (||c_a|| + ||c_b||)^2 its error bound. ``srml_dbscan_tile_pairs``: a count pass, a
+    scan of the counts, a fill pass."""
+    T, n = centres.shape
+    thr = float(np.sqrt(float(eps2) + float(band)))
+    if not centres.is_cuda:
+        C = centres.float()
+        cn = cnorm.float()
+        d2 = (cn.view(-1, 1) + cn.view(1, -1) - 2.0 * (C @ C.T)).double()
+        sc = cn.double().sqrt()
+        e = (1.5 * n + 5.0) * 2.0 ** -24 * (sc.view(-1, 1) + sc.view(1, -1)) ** 2
+        reach = radii.double().view(-1, 1) + radii.double().view(1, -1) + thr
+        keep = torch.tril((d2 - e <= reach * reach) | torch.eye(T, dtype=torch.bool))
+        ab = torch.nonzero(keep)  # row-major: ascending in a (a + 1) / 2 + b
+        return ab[:, 0] * (ab[:, 0] + 1) // 2 + ab[:, 1]
+    C = _c(centres.float())
+    r = _c(radii.float())
+    cn = _c(cnorm.float())
+    TB = (T + DB_TILE - 1) // DB_TILE
+    counts = zeros(T * TB, dtype=torch.int32, device=C.device)
+    st = native.stream(C.device)
+    native.call("srml_dbscan_tile_pairs", C.data_ptr(), T, n, C.stride(0), r.data_ptr(), cn.data_ptr(), thr,
+                counts.data_ptr(), None, None, 0, st)
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    offs = ends - counts
+    out = torch.empty(int(ends[-1].item()) if T else 0, dtype=torch.int64, device=C.device)
+    native.call("srml_dbscan_tile_pairs", C.data_ptr(), T, n, C.stride(0), r.data_ptr(), cn.data_ptr(), thr,
+                counts.data_ptr(), offs.data_ptr(), out.data_ptr(), 1, st)
+    return out
+
+
+def _check_pair_list(N: int, pairs: torch.Tensor, l0: int, l1: int, perm: torch.Tensor) -> None:
+    """The list kernels index with ``pairs[l0: l1]`` and ``perm`` as they are: refuse what would leave the arrays."""
+    if not 0 <= l0 <= l1 <= pairs.shape[0] or perm.shape[0] != N:
+        raise ValueError("dbscan list sweep: range [%d, %d) of %d pairs, %d ids for %d rows"
+                         % (l0, l1, pairs.shape[0], perm.shape[0], N))
+    if l1 > l0 and N:
+        part = pairs[l0: l1]
+        ok = (part.min() >= 0) & (part.max() < dbscan_num_tiles(N)) & (perm.min() >= 0) & (perm.max() < N)
+        if not bool(ok.item()):
+            raise ValueError("dbscan list sweep: a tile-pair index or a row id is out of range")
+
+
+def dbscan_degree_list(Xp: torch.Tensor, xnp: torch.Tensor, eps2: float, pairs: torch.Tensor, l0: int, l1: int,
+                       perm: torch.Tensor, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dbscan_degree`` over the tile pairs ``pairs[l0: l1]`` of the permuted rows ``Xp`` = X[perm]: distances at
+    positions, ``counts`` indexed by original id ``perm[position]``. ``srml_dbscan_degree_list_f32``."""
+    N = Xp.shape[0]
+    if counts is None:
+        counts = zeros(N, dtype=torch.int32, device=Xp.device)
+    if not Xp.is_cuda:
+        return _degree_cpu(Xp, xnp, eps2, l0, l1, counts, pairs.tolist(), perm.long())
+    Xp = _c(Xp.float())
+    _check_pair_list(N, pairs, l0, l1, perm)
+    native.call("srml_dbscan_degree_list_f32", Xp.data_ptr(), N, Xp.shape[1], Xp.stride(0), _c(xnp.float()).data_ptr(),
+                float(eps2), _c(pairs.long()).data_ptr(), int(l0), int(l1), _c(perm.int()).data_ptr(),
+                counts.data_ptr(), native.stream(Xp.device))
+    return counts
+
+
+def dbscan_link_list(Xp: torch.Tensor, xnp: torch.Tensor, eps2: float, pairs: torch.Tensor, l0: int, l1: int,
+                     perm: torch.Tensor, core: torch.Tensor, parent: torch.Tensor, best: torch.Tensor) -> None:
+    """``dbscan_link`` over the tile pairs ``pairs[l0: l1]`` of the permuted rows: ``core``, ``parent`` and ``best`` are
+    indexed by original id, and so are the roots (smallest original core index) and the neighbour in
+    every border key (ties to the lowest original index). ``srml_dbscan_link_list_f32``."""
+    N = Xp.shape[0]
+    if not Xp.is_cuda:
+        _link_cpu(Xp, xnp, eps2, l0, l1, core, parent, best, pairs.tolist(), perm.long())
+        return
+    Xp = _c(Xp.float())
+    _check_pair_list(N, pairs, l0, l1, perm)
+    native.call("srml_dbscan_link_list_f32", Xp.data_ptr(), N, Xp.shape[1], Xp.stride(0), _c(xnp.float()).data_ptr(),
+                float(eps2), _c(pairs.long()).data_ptr(), int(l0), int(l1), _c(perm.int()).data_ptr(),
+                _c(core.to(torch.uint8)).data_ptr(), parent.data_ptr(), best.data_ptr(), native.stream(Xp.device))
 
 
 # ------------------------------------------------------------------------------------------

@@ -14,108 +14,22 @@
 //     Border points keep the nearest core neighbour as a packed (orderable dist << 32 | index)
 //     64-bit atomicMin key.
 //   srml_uf_unite_pairs / srml_uf_compress: merge another rank's forest, flatten to roots.
-#include "common.h"
-#include "tile.h"
+// The per-tile bodies live in dbscan_tile.h (shared with the list-driven sweeps of dbscan_rbc.hip).
+#include "dbscan_tile.h"
 
 namespace {
-using namespace srml_tile;
-
-__device__ __forceinline__ void tri_decode(long t, long& bi, long& bj) {
-  double d = sqrt(8.0 * (double)t + 1.0);
-  long i = (long)((d - 1.0) * 0.5);
-  while (i > 0 && i * (i + 1) / 2 > t) --i;
-  while ((i + 1) * (i + 2) / 2 <= t) ++i;
-  bi = i;
-  bj = t - i * (i + 1) / 2;
-}
-
-union DbSmem {
-  Stage128 st;
-  float D[128][129];
-};
-
-template <bool VEC>
-__device__ __forceinline__ void distance_tile(const float* __restrict__ X, long N, int n, long ld,
-                                              const float* __restrict__ xnorm, float eps2, long r0, long c0,
-                                              DbSmem& sm) {
-  floatx16 acc[2][2];
-  gemm_tile_128<VEC>(X, ld, N, r0, X, ld, N, c0, n, sm.st, acc);
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int cl = acc_col(nt);
-    const long gc = c0 + cl;
-    const float cn = gc < N ? xnorm[gc] : 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = acc_row(mt, r);
-        const long gr = r0 + rl;
-        const float rn = gr < N ? xnorm[gr] : 0.f;
-        // a point is its own neighbour at every eps >= 0: the expanded form of D(i, i) is rounding noise
-        const float d = gr == gc ? 0.f : fmaxf(fmaf(-2.f, acc[mt][nt][r], rn + cn), 0.f);
-        sm.D[rl][cl] = (gr < N && gc < N && d <= eps2) ? d : __builtin_huge_valf();
-      }
-  }
-  __syncthreads();
-}
+using namespace srml_dbscan;
 
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void dbscan_degree_kernel(const float* __restrict__ X, long N, int n, long ld,
                                                                const float* __restrict__ xnorm, float eps2, long t0,
                                                                long t1, int* __restrict__ counts) {
   __shared__ DbSmem sm;
-  const int t = threadIdx.x;
   for (long tile = t0 + blockIdx.x; tile < t1; tile += gridDim.x) {
     long bi, bj;
     tri_decode(tile, bi, bj);
-    const long r0 = bi * 128, c0 = bj * 128;
-    distance_tile<VEC>(X, N, n, ld, xnorm, eps2, r0, c0, sm);
-    if (t < 128) {
-      int cnt = 0;
-      for (int c = 0; c < 128; ++c) cnt += sm.D[t][c] != __builtin_huge_valf();
-      if (cnt) atomicAdd(&counts[r0 + t], cnt);
-    } else if (bi != bj) {
-      const int c = t - 128;
-      int cnt = 0;
-      for (int r = 0; r < 128; ++r) cnt += sm.D[r][c] != __builtin_huge_valf();
-      if (cnt) atomicAdd(&counts[c0 + c], cnt);
-    }
-    __syncthreads();
+    degree_tile<VEC>(X, N, n, ld, xnorm, eps2, bi, bj, IdentityIds{bi * 128, bj * 128}, counts, sm);
   }
-}
-
-// ---- union-find -------------------------------------------------------------------------------
-__device__ __forceinline__ int uf_find(volatile int* p, int x) {
-  int y = p[x];
-  while (y != x) {
-    const int z = p[y];
-    if (z != y) p[x] = z;  // path halving; parents only ever point to smaller indices
-    x = y;
-    y = z;
-  }
-  return x;
-}
-
-__device__ __forceinline__ void uf_unite(int* p, int a, int b) {
-  volatile int* vp = p;
-  a = uf_find(vp, a);
-  b = uf_find(vp, b);
-  while (a != b) {
-    if (a < b) {
-      const int s = a;
-      a = b;
-      b = s;
-    }
-    const int old = atomicCAS(&p[a], a, b);  // hook the larger root under the smaller
-    if (old == a) return;
-    a = uf_find(vp, old);
-    b = uf_find(vp, b);
-  }
-}
-
-__device__ __forceinline__ unsigned long long nn_key(float d, long idx) {
-  return ((unsigned long long)orderable(d) << 32) | (unsigned long long)(unsigned)idx;
 }
 
 template <bool VEC>
@@ -125,60 +39,11 @@ __global__ __launch_bounds__(256, 2) void dbscan_link_kernel(const float* __rest
                                                              int* __restrict__ parent,
                                                              unsigned long long* __restrict__ best) {
   __shared__ DbSmem sm;
-  __shared__ int lp[256];
-  __shared__ unsigned char lcore[256];
-  __shared__ unsigned long long cbest[128];
-  const int t = threadIdx.x;
+  __shared__ LinkSmem ls;
   for (long tile = t0 + blockIdx.x; tile < t1; tile += gridDim.x) {
     long bi, bj;
     tri_decode(tile, bi, bj);
-    const long r0 = bi * 128, c0 = bj * 128;
-    const long gid = t < 128 ? r0 + t : c0 + (t - 128);
-    lcore[t] = gid < N ? core[gid] : 0;
-    lp[t] = (bi == bj && t >= 128) ? t - 128 : t;  // diagonal tile: column slot c is row slot c
-    if (t < 128) cbest[t] = ~0ull;
-    distance_tile<VEC>(X, N, n, ld, xnorm, eps2, r0, c0, sm);  // ends with __syncthreads
-    if (t < 128 && r0 + t < N) {
-      const bool rc = lcore[t];
-      unsigned long long rb = ~0ull;
-      for (int c = 0; c < 128; ++c) {
-        const float d = sm.D[t][c];
-        if (d == __builtin_huge_valf()) continue;
-        const bool cc = lcore[128 + c];
-        if (rc && cc) {
-          // local union in LDS (same CAS scheme on slot indices)
-          volatile int* vp = lp;
-          int a = uf_find(vp, t), b = uf_find(vp, 128 + c);
-          while (a != b) {
-            if (a < b) {
-              const int s = a;
-              a = b;
-              b = s;
-            }
-            const int old = atomicCAS(&lp[a], a, b);
-            if (old == a) break;
-            a = uf_find(vp, old);
-            b = uf_find(vp, b);
-          }
-        } else if (!rc && cc) {
-          const unsigned long long key = nn_key(d, c0 + c);
-          rb = key < rb ? key : rb;
-        } else if (rc && !cc) {
-          atomicMin(&cbest[c], nn_key(d, r0 + t));
-        }
-      }
-      if (rb != ~0ull) atomicMin(&best[r0 + t], rb);
-    }
-    __syncthreads();
-    if (t < 128 && cbest[t] != ~0ull) atomicMin(&best[c0 + t], cbest[t]);
-    if (gid < N && lcore[t]) {
-      const int r = uf_find((volatile int*)lp, t);
-      if (r != t) {
-        const long g2 = r < 128 ? r0 + r : c0 + (r - 128);
-        if (g2 != gid) uf_unite(parent, (int)gid, (int)g2);
-      }
-    }
-    __syncthreads();
+    link_tile<VEC>(X, N, n, ld, xnorm, eps2, bi, bj, IdentityIds{bi * 128, bj * 128}, core, parent, best, sm, ls);
   }
 }
 
@@ -192,15 +57,6 @@ __global__ void uf_unite_pairs_kernel(int* __restrict__ parent, long N, const in
 __global__ void uf_compress_kernel(int* __restrict__ parent, long N) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x)
     parent[i] = uf_find((volatile int*)parent, (int)i);
-}
-
-inline bool vec_ok(const float* X, long ld, int n) {
-  return ((ld & 3) == 0) && ((n & 3) == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
-}
-
-inline unsigned grid_for(long tiles) {
-  long g = tiles < 8192 ? tiles : 8192;
-  return (unsigned)(g < 1 ? 1 : g);
 }
 }  // namespace
 

@@ -143,6 +143,12 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_center_rows_f16": (_P, _I, _L, _P, _P, _I, _L, _P, _P, _P),
     "srml_dbscan_degree_f32": (_P, _L, _I, _L, _P, _F, _L, _L, _P, _P),
     "srml_dbscan_link_f32": (_P, _L, _I, _L, _P, _F, _L, _L, _P, _P, _P, _P),
+    # rbc: tile balls (X, N, n, ld, centres, radii, cnorm), tile-pair list (C, T, n, ld, radii, cnorm, thr, counts,
+    # offsets, out, fill) and the sweeps over a pair list (.., pairs, l0, l1, perm, ..)
+    "srml_dbscan_tile_balls_f32": (_P, _L, _I, _L, _P, _P, _P, _P),
+    "srml_dbscan_tile_pairs": (_P, _L, _I, _L, _P, _P, _D, _P, _P, _P, _I, _P),
+    "srml_dbscan_degree_list_f32": (_P, _L, _I, _L, _P, _F, _P, _L, _L, _P, _P, _P),
+    "srml_dbscan_link_list_f32": (_P, _L, _I, _L, _P, _F, _P, _L, _L, _P, _P, _P, _P, _P),
     "srml_uf_unite_pairs": (_P, _L, _P, _P),
     "srml_uf_compress": (_P, _L, _P),
     "srml_dbscan_labels_ws": (_L,),
