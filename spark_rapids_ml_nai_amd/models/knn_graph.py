@@ -15,6 +15,10 @@
   from a dense graph of a seeded random projection of the rows, then NN-descent rounds on the CSR
   rows in the route's own metric (``ops.csr_nnd_join``).
 
+* ``knn_graph_metric_approx`` — approximate, dense rows in the ``ops.pairwise_dist`` metrics
+  (``build_algo="metric_nn_descent"``): candidates from a Euclidean graph of proxy rows, then NN-descent
+  rounds on the rows in the route's own metric (``ops.nnd_join``).
+
 The reference fits UMAP on one GPU with cuML's own kNN (``umap.py:840-850,924-958``).
 """
 from __future__ import annotations
@@ -573,6 +577,75 @@ def knn_graph_csr_approx(X: Any, k: int, metric: str = "euclidean", seed: int = 
     return (torch.sqrt(keys.clamp_min(0)) if kind == "euclidean" else keys), pos
 
 
+METRIC_ALGO = "metric_nn_descent"
+
+
+def metric_proxy_rows(Xp: torch.Tensor, name: str) -> torch.Tensor:
+    """The rows whose Euclidean graph seeds the candidates of ``knn_graph_metric_approx``: the prepared
+    rows themselves (hellinger: the square roots, whose Euclidean distance is the Hellinger distance up
+    to the rows' masses), for jaccard the indicators scaled by 1 / sqrt(nnz) (unit rows whose dot is
+    the overlap share; all-zero rows stay zero)."""
+    if name != "jaccard":
+        return Xp
+    ind = (Xp != 0).to(Xp.dtype)
+    nnz = ind.sum(1, keepdim=True)
+    return ind * torch.where(nnz > 0, torch.rsqrt(nnz.clamp_min(1.0)), torch.zeros_like(nnz))
+
+
+def knn_graph_metric_approx(X: torch.Tensor, k: int, metric: str, p: float = 2.0, seed: int = 0, ctx: Any = None,
+                            phases: Optional[dict] = None, nnd_iters: Optional[int] = None, a: int = 8, b: int = 8,
+                            R: int = 16, dense_kwds: Optional[dict] = None, cand_k: Optional[int] = None,
+                            rounds: Optional[list] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Approximate all-points graph of dense rows in a metric of ``ops.pairwise_dist``: (distances
+    [N, k] fp32, indices [N, k] int64). The construction of ``knn_graph_csr_approx`` on dense rows:
+
+    1. candidates: ``build_knn_graph(S, cand_k, "auto", dense_kwds)`` on the Euclidean proxy rows S
+       (``metric_proxy_rows``; exact up to 100 000 rows, per-query-probed IVF lists beyond). Only the
+       neighbour ids are kept (``cand_k``: k);
+    2. round 0 re-scores the candidates in the route's own metric (the join with a = 0, R = 0), so
+       every distance that leaves here is the metric's own;
+    3. ``nnd_iters`` NN-descent rounds follow (own list, first ``a`` neighbours' first ``b``
+       neighbours, up to ``R`` reverse neighbours), each one ``ops.nnd_join`` launch. Distributed, every
+       rank refines its ``row_split`` block of the replicated graph and the blocks are all-gathered
+       after every round.
+
+    ``rounds`` (a list) receives ("candidates", None, ids) and then (name, keys, ids) of the whole
+    graph after round 0 and every later round.
+    Rows short of k candidates (tiny IVF lists) end with -1 at the row's largest distance."""
+    import time
+
+    name, p = ops.pairdist_metric(metric, p)
+    N = X.shape[0]
+    dev = X.device
+    nnd_iters = NND_ITERS if nnd_iters is None else int(nnd_iters)
+    t0 = time.perf_counter()
+    Xp = ops._pairdist_prepare(X, name).contiguous()
+    kc = max(1, min(int(cand_k) if cand_k else k, N))
+    sub: dict = {}
+    _, cand = build_knn_graph(metric_proxy_rows(Xp, name), kc, "auto", dense_kwds, seed, ctx, phases=sub)
+    lo, hi = row_split(N, ctx)
+    t0 = record_phase(phases, "metric_candidates", hi - lo, t0, dev)
+    if phases is not None:
+        phases.update({"metric_candidates." + key: val for key, val in sub.items()})
+    Q = Xp[lo:hi]
+    if rounds is not None:
+        rounds.append(("candidates", None, cand))
+    keys, pos = ops.nnd_join(Q, Xp, cand, None, None, k, 0, 0, 0, name, p, row0=lo)
+    keys, pos = gather_rows(keys, ctx), gather_rows(pos, ctx)
+    if rounds is not None:
+        rounds.append(("round0", keys, pos))
+    for it in range(max(0, nnd_iters)):
+        perm, off = reverse_lists(pos)
+        keys, pos = ops.nnd_join(Q, Xp, pos, perm, off, k, a, b, R, name, p, row0=lo)
+        keys, pos = gather_rows(keys, ctx), gather_rows(pos, ctx)
+        if rounds is not None:
+            rounds.append(("round%d" % (it + 1), keys, pos))
+    record_phase(phases, "metric_nn_descent", hi - lo, t0, dev)
+    fin = torch.isfinite(keys)
+    rowmax = torch.where(fin, keys, torch.zeros_like(keys)).max(1, keepdim=True).values
+    return torch.where(fin, keys, rowmax), pos
+
+
 def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Optional[dict] = None,
                     seed: int = 0, ctx: Any = None, list_order: bool = False, phases: Optional[dict] = None,
                     metric: str = "euclidean", p: float = 2.0) -> Any:
@@ -580,9 +653,12 @@ def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Option
     builder left the graph in a locality order (see ``knn_graph_ivf``).
 
     ``metric`` / ``p``: a metric of ``ops.pairwise_dist`` is served by the exact chunked search
-    only: ``auto`` and ``brute_force_knn`` run it at ANY row count, which is O(N^2 n) work (the
-    100k-row switch to IVF lists applies to the Euclidean family alone); the IVF lists and the
-    NN-descent re-scoring are Euclidean throughout, so ``ivf`` / ``nn_descent`` raise.
+    by ``auto`` and ``brute_force_knn`` at ANY row count, which is O(N^2 n) work (the 100k-row switch
+    to IVF lists applies to the Euclidean family alone); the IVF lists and the NN-descent re-scoring
+    are Euclidean throughout, so ``ivf`` / ``nn_descent`` raise. ``metric_nn_descent``
+    (``knn_graph_metric_approx``; ``build_kwds`` ``nnd_iters``, ``a``, ``b``, ``R``, ``cand_k``, and
+    ``nlist`` / ``nprobe`` / ``probe`` for the Euclidean candidate build) is their approximate graph
+    on dense rows; it serves these metrics only.
 
     A CSR ``X`` (metric kinds ``euclidean`` — the caller may have unit-scaled the rows for cosine —
     ``hellinger`` and ``jaccard``) is served by the exact CSR search (``auto``, ``brute_force_knn``; at
@@ -593,6 +669,19 @@ def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Option
     if algo == RP_ALGO and not is_csr(X):
         raise ValueError("build_algo %r builds graphs of sparse (CSR) rows only; dense rows have 'ivf' and "
                          "'nn_descent'" % (build_algo,))
+    if algo == METRIC_ALGO:
+        if is_csr(X):
+            raise ValueError("build_algo %r builds graphs of dense rows only; sparse (CSR) rows have "
+                             "'rp_nn_descent'" % (build_algo,))
+        if is_euclidean(metric):
+            raise ValueError("build_algo %r builds graphs in the non-Euclidean metrics (%s) only; metric %r has "
+                             "'nn_descent'" % (build_algo, ", ".join(sorted(ops.PAIRDIST_CODES)), metric))
+        kw = dict(build_kwds or {})
+        dense_kwds = {key: kw[key] for key in ("nlist", "nprobe", "probe") if kw.get(key) is not None}
+        d, i = knn_graph_metric_approx(X, k, metric, p, seed=seed, ctx=ctx, phases=phases,
+                                       nnd_iters=kw.get("nnd_iters"), a=int(kw.get("a", 8)), b=int(kw.get("b", 8)),
+                                       R=int(kw.get("R", 16)), dense_kwds=dense_kwds, cand_k=kw.get("cand_k"))
+        return (d, i, None) if list_order else (d, i)
     if is_csr(X):
         kind = sparse_kind(metric)
         if algo in ("ivf", "ivfflat", "ivf_flat", "nn_descent"):
@@ -637,4 +726,4 @@ def build_knn_graph(X: Any, k: int, build_algo: str = "auto", build_kwds: Option
         return knn_graph_ivf(X, k, nlist=kw.get("nlist"), nprobe=kw.get("nprobe"), seed=seed, ctx=ctx,
                              list_order=list_order, phases=phases, probe=kw.get("probe"), nnd_iters=nnd)
     raise ValueError("Unsupported build_algo %r (auto, brute_force_knn, ivf, nn_descent; rp_nn_descent for sparse "
-                     "rows)" % build_algo)
+                     "rows; metric_nn_descent for dense rows in a non-Euclidean metric)" % build_algo)

@@ -4083,6 +4083,107 @@ def csr_nnd_join(Q_rows: Any, I: Any, pos: torch.Tensor, perm: Optional[torch.Te
 
 
 # ------------------------------------------------------------------------------------------
+# NN-descent join on dense rows (csrc/nnd.hip): UMAP's approximate graph in the pairwise_dist metrics
+# dispatch constants of csrc/nnd.hip (srml_nnd_config returns the same three)
+NND_CAND_CAP = 512          # candidate slots kw + a b + R of one row (ND_CAND)
+NND_STAGE_CAP = 8192        # query features the join kernel stages in LDS (ND_STAGE)
+NND_KMAX = 64               # widest output list (ND_KMAX)
+NND_CODES = dict(PAIRDIST_CODES, sqeuclidean=9)  # name -> code of srml_nnd_join_f32
+_NND_TORCH_ROWS = 4096      # rows of one chunk of the torch form
+
+
+def _nnd_expr(q: torch.Tensor, I: torch.Tensor, name: str, p: float) -> torch.Tensor:
+    if name == "sqeuclidean":  # direct form
+        return ((q.unsqueeze(1) - I.unsqueeze(0)) ** 2).sum(-1)
+    return _pairdist_expr(q, I, name, p)
+
+
+def _nnd_join_torch(Qp: torch.Tensor, Ip: torch.Tensor, pos: torch.Tensor, perm: Optional[torch.Tensor],
+                    off: Optional[torch.Tensor], k: int, a: int, b: int, R: int, name: str, p: float,
+                    row0: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    N = pos.shape[0]
+    rows, dev = Qp.shape[0], pos.device
+    Ip = Ip.to(Qp.dtype)
+    outk = torch.full((rows, k), float("inf"), dtype=torch.float32, device=dev)
+    outi = torch.full((rows, k), -1, dtype=torch.int64, device=dev)
+    for s in range(0, rows, _NND_TORCH_ROWS):
+        e = min(rows, s + _NND_TORCH_ROWS)
+        cand = csr_nnd_candidates(pos, perm, off, row0 + s, row0 + e, a, b, R)
+        cand = torch.sort(torch.where(cand >= 0, cand, torch.full_like(cand, N)), dim=1).values  # empty slots trail
+        dup = torch.zeros_like(cand, dtype=torch.bool)
+        dup[:, 1:] = cand[:, 1:] == cand[:, :-1]
+        live = (cand < N) & ~dup
+        for r in range(s, e):
+            ids = cand[r - s][live[r - s]]  # ascending and unique: a stable sort by key orders by (key, id)
+            if not ids.numel():
+                continue
+            d, j = torch.sort(_nnd_expr(Qp[r: r + 1], Ip.index_select(0, ids), name, p)[0].float(), stable=True)
+            kk = min(k, ids.numel())
+            outk[r, :kk] = d[:kk]
+            outi[r, :kk] = ids[j[:kk]]
+    return outk, outi
+
+
+def nnd_join(Q_rows: torch.Tensor, I: torch.Tensor, pos: torch.Tensor, perm: Optional[torch.Tensor],
+             off: Optional[torch.Tensor], k: int, a: int, b: int, R: int, metric: str, p: float = 2.0,
+             row0: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One NN-descent join on dense rows, the twin of ``csr_nnd_join``: for every row of the block
+    ``Q_rows`` (graph rows ``row0 .. row0 + rows`` of ``I``'s all-points graph ``pos``, int64 [N, kw])
+    the ``k`` nearest among its own list, its first ``a`` neighbours' first ``b`` neighbours and up to
+    ``R`` reverse neighbours (``perm`` / ``off``: the N kw edges grouped by target, as ``label_sort``
+    returns them), re-ranked by the metric of the rows: (keys fp32 [rows, k], ids int64 [rows, k])
+    ascending by (key, id), equal keys to the lower id, missing places +inf / -1. -1 entries and ids
+    outside [0, N) are dropped and the ids de-duplicated before any distance is computed; a row that
+    lists itself keeps itself at its true distance. ``a`` and ``b`` are cut to the list width.
+
+    ``metric`` / ``p``: a metric of ``pairwise_dist`` (its table; the keys are the distances) or
+    ``sqeuclidean`` (squared distances in direct form). The rows are PREPARED rows
+    (``_pairdist_prepare``: hellinger holds the square roots).
+
+    fp32 device rows within the kernel's limits (k <= ``NND_KMAX``, kw + a b + R <= ``NND_CAND_CAP``)
+    run ``srml_nnd_join_f32``: one workgroup per row, sub-wave teams per candidate, no atomics, the
+    output a pure function of the inputs. Anything else runs a torch form of the same contract."""
+    name, p = ("sqeuclidean", 2.0) if str(metric).lower() == "sqeuclidean" else pairdist_metric(metric, p)
+    if Q_rows.dim() != 2 or I.dim() != 2 or Q_rows.shape[1] != I.shape[1]:
+        raise ValueError("nnd_join: rows %s against items %s" % (tuple(Q_rows.shape), tuple(I.shape)))
+    if pos.dim() != 2 or pos.shape[0] != I.shape[0] or pos.shape[1] < 1:
+        raise ValueError("nnd_join: the graph must be [%d, kw >= 1], got %s" % (I.shape[0], tuple(pos.shape)))
+    N, kw = pos.shape
+    rows, n, row0, k = Q_rows.shape[0], Q_rows.shape[1], int(row0), int(k)
+    if k < 1:
+        raise ValueError("nnd_join: k=%d" % k)
+    if row0 < 0 or row0 + rows > N:
+        raise ValueError("nnd_join: rows %d .. %d outside the graph's %d rows" % (row0, row0 + rows, N))
+    a, b, R = max(0, min(int(a), kw)), max(0, min(int(b), kw)), max(0, int(R))
+    if a * b == 0:
+        a = b = 0
+    pos = _c(pos.to(torch.int64))
+    if R > 0:
+        if perm is None or off is None or perm.numel() != N * kw or off.numel() != N + 1:
+            raise ValueError("nnd_join: R > 0 needs perm (N kw edges) and off (N + 1 starts)")
+        perm, off = _c(perm.to(torch.int64)), _c(off.to(torch.int64))
+    else:
+        perm = off = None
+    if not (rows and n and Q_rows.is_cuda and I.is_cuda and pos.is_cuda and Q_rows.dtype == torch.float32
+            and I.dtype == torch.float32 and k <= NND_KMAX and kw + a * b + R <= NND_CAND_CAP and N < 2 ** 31 - 1):
+        return _nnd_join_torch(Q_rows, I, pos, perm, off, k, a, b, R, name, p, row0)
+    Qp, Ip = _unit_cols(Q_rows), _unit_cols(I)
+    dev = Qp.device
+    outk = torch.empty((rows, k), dtype=torch.float32, device=dev)
+    outi = torch.empty((rows, k), dtype=torch.int64, device=dev)
+    rc = native.call_status("srml_nnd_join_f32", Qp.data_ptr(), rows, row0, Qp.stride(0), Ip.data_ptr(), N, n,
+                            Ip.stride(0), pos.data_ptr(), kw, perm.data_ptr() if perm is not None else None,
+                            off.data_ptr() if off is not None else None, k, a, b, R, NND_CODES[name], float(p),
+                            outk.data_ptr(), outi.data_ptr(), native.stream(dev))
+    if rc < 0:
+        raise ValueError("srml_nnd_join_f32 refused the launch (status %d: -1 grid overflow, -2 metric / arguments / "
+                         "p, -3 candidate slots or k)" % rc)
+    if rc != 0:
+        raise RuntimeError("srml_nnd_join_f32 launch failed with HIP status %d" % rc)
+    return outk, outi
+
+
+# ------------------------------------------------------------------------------------------
 # KMeans on CSR rows against dense centres (csrc/csr_kmeans.hip)
 # dispatch constants of csrc/csr_kmeans.hip (srml_csr_kmeans_config returns the same three)
 CSR_KM_TK = 256             # centres per pass of the search: 64 lanes x 4 accumulators (KM_TK)

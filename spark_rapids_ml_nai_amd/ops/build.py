@@ -44,9 +44,17 @@ def _headers() -> List[str]:
     return sorted(glob.glob(os.path.join(CSRC, "*.h")))
 
 
-def _flags() -> List[str]:
+# Translation units built without the packed fp32 VALU instructions (v_pk_add / mul / fma_f32): their
+# inner loops are per-lane scalar chains, and the keys they sort must be the scalar results.
+NO_PACKED_FP32 = ("nnd.hip",)
+
+
+def _flags(src: str = "") -> List[str]:
+    extra = []
+    if os.path.basename(src) in NO_PACKED_FP32:
+        extra = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=fast",
-            "-munsafe-fp-atomics"]
+            "-munsafe-fp-atomics"] + extra
 
 
 def needs_build() -> bool:
@@ -62,7 +70,7 @@ def _compile(src: str) -> str:
     hdr_t = max([os.path.getmtime(h) for h in _headers()] + [0])
     if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), hdr_t, os.path.getmtime(__file__)):
         return obj
-    cmd = [hipcc()] + _flags() + ["-c", src, "-o", obj]
+    cmd = [hipcc()] + _flags(src) + ["-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, " ".join(cmd), r.stderr[-8000:]))

@@ -27,50 +27,17 @@
 // ABSOLUTE row offsets (see csr_knn.hip); ids index the item matrix.
 #include "common.h"
 #include "csr_pair.h"  // ck_lower_bound, rf_pair, rf_dot
+#include "nnd_lds.h"   // NJ_T, NJ_NONE, NJ_EMPTY, nj_sort, nj_orderable, nj_float
 
 namespace {
 enum : int { NJ_SQEUCLIDEAN = 0, NJ_HELLINGER = 1, NJ_JACCARD = 2 };
 
-constexpr int NJ_T = 256;        // threads per block
 constexpr int NJ_WAVES = NJ_T / 64;
 constexpr int NJ_CAND = 512;     // candidate slots (kw + a b + R) per row; a power of two
 constexpr int NJ_CAP = 2048;     // query non-zeros staged in LDS (index + value: 16 KiB)
 constexpr int NJ_KMAX = 64;      // output width
-constexpr int NJ_NONE = 0x7fffffff;  // an empty slot: sorts after every id
-constexpr unsigned long long NJ_EMPTY = ~0ull;  // an empty key: no id has all 32 low bits set
 constexpr int NJ_LDS = NJ_CAP * 8 + NJ_CAND * 12;
 constexpr int NJ_LDS_MAX = 64 * 1024;  // static LDS of one workgroup
-
-// ascending bitonic sort of s[0 .. P), P a power of two >= 2, by the whole block
-template <typename T>
-__device__ __forceinline__ void nj_sort(T* s, int P, int t) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int p = t; p < (P >> 1); p += NJ_T) {
-        const int i = 2 * p - (p & (stride - 1));  // the pair's lower index: bit `stride` clear
-        const int j = i + stride;
-        const bool up = (i & size) == 0;
-        const T x = s[i], y = s[j];
-        if ((x > y) == up) {
-          s[i] = y;
-          s[j] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// fp32 bits whose unsigned order is the order of the floats (-0 < +0, NaNs at the ends)
-__device__ __forceinline__ unsigned nj_orderable(float d) {
-  const unsigned b = (unsigned)__float_as_int(d);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float nj_float(unsigned o) {
-  return __int_as_float((int)((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o));
-}
 
 template <int M, typename PI, typename PV>
 __device__ __forceinline__ float nj_key(PI xi, PV xv, long nx, float qa, const int* __restrict__ yi,

@@ -26,56 +26,10 @@
 // union; HELLINGER expects the square roots of the rows and accumulates their product.
 // Reference: the metrics of cuML UMAP (umap.py:169-179 of the reference), scipy's definitions.
 #include "common.h"
+#include "pair_metric.h"  // PD_* codes, pd_pre, pd_term, pd_final
 
 namespace {
-enum : int { PD_L1 = 0, PD_LINF = 1, PD_MINKOWSKI = 2, PD_CANBERRA = 3, PD_HAMMING = 4, PD_JACCARD = 5,
-             PD_HELLINGER = 6, PD_MINK3 = 7, PD_MINK4 = 8 };  // 7, 8: MINKOWSKI with p = 3 / 4 on multiplies
-
 constexpr int PD_TQ = 64, PD_TI = 128, PD_KC = 32, PD_T = 256;
-
-template <int M>
-__device__ __forceinline__ float pd_pre(float x) {
-  if constexpr (M == PD_JACCARD) return x != 0.f ? 1.f : 0.f;
-  return x;
-}
-
-template <int M>
-__device__ __forceinline__ void pd_term(float& acc, float a, float b, float p) {
-  if constexpr (M == PD_L1) {
-    acc += fabsf(a - b);
-  } else if constexpr (M == PD_LINF) {
-    acc = fmaxf(acc, fabsf(a - b));
-  } else if constexpr (M == PD_MINKOWSKI) {
-    acc += powf(fabsf(a - b), p);
-  } else if constexpr (M == PD_MINK3) {
-    const float t = fabsf(a - b);
-    acc += t * t * t;
-  } else if constexpr (M == PD_MINK4) {
-    const float t = (a - b) * (a - b);
-    acc += t * t;
-  } else if constexpr (M == PD_CANBERRA) {
-    const float s = fabsf(a) + fabsf(b);
-    acc += s > 0.f ? fabsf(a - b) / s : 0.f;
-  } else if constexpr (M == PD_HAMMING) {
-    acc += a != b ? 1.f : 0.f;
-  } else {  // JACCARD (indicators), HELLINGER (square roots)
-    acc = fmaf(a, b, acc);
-  }
-}
-
-template <int M>
-__device__ __forceinline__ float pd_final(float acc, float qnz, float inz, int n, float p) {
-  if constexpr (M == PD_MINKOWSKI) return powf(acc, 1.f / p);
-  if constexpr (M == PD_MINK3) return cbrtf(acc);
-  if constexpr (M == PD_MINK4) return sqrtf(sqrtf(acc));
-  if constexpr (M == PD_HAMMING) return acc / (float)n;
-  if constexpr (M == PD_JACCARD) {
-    const float uni = qnz + inz - acc;
-    return uni > 0.f ? (uni - acc) / uni : 0.f;
-  }
-  if constexpr (M == PD_HELLINGER) return sqrtf(fmaxf(0.f, 1.f - acc));
-  return acc;
-}
 
 // global -> registers: the ROWS x 32 block at (row0, k0) of a row-major matrix; element e of the
 // thread is (row f % ROWS, feature f / ROWS [VEC: 4 features from 4 (f / ROWS)]) of

@@ -223,6 +223,10 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_csr_nnd_config": (_I,),
     "srml_csr_nnd_join_f32": (_P, _P, _P, _P, _L, _L, _P, _P, _P, _P, _L, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P,
                               _P),
+    # NN-descent join on dense rows: query block (Q, rows, row0, ldq), item matrix (I, N, n, ldi), graph (pos, kw,
+    # perm, off), k, a, b, R, metric, p, out keys / ids
+    "srml_nnd_config": (_I,),
+    "srml_nnd_join_f32": (_P, _L, _L, _L, _P, _L, _I, _L, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P),
     # KMeans on CSR rows: (row offsets, indices, values, rows), then CT, centre norms, k, kp, labels, distances /
     # n, nnz, labels, k, fixed-point scale (0: fp64 atomics), sums
     "srml_csr_kmeans_config": (_I,),

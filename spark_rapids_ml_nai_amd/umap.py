@@ -106,12 +106,17 @@ class _UMAPParams(_FeaturesColMixin, _BackendParams, HasFeaturesCol, HasFeatures
                     "'brute_force_knn', 'ivf' (per-query IVF probing) or 'nn_descent' (the IVF graph refined by "
                     "NN-descent rounds). Sparse rows (enable_sparse_data_optim): 'auto' / 'brute_force_knn' (the "
                     "exact CSR search at any row count) or 'rp_nn_descent' (approximate: candidates from a seeded "
-                    "random projection, NN-descent rounds on the CSR rows in the fit's metric).",
+                    "random projection, NN-descent rounds on the CSR rows in the fit's metric). Dense rows in a "
+                    "non-Euclidean metric (l1, chebyshev, minkowski, canberra, hamming, jaccard, hellinger): 'auto' / "
+                    "'brute_force_knn' (exact at any row count) or 'metric_nn_descent' (approximate: candidates from a "
+                    "Euclidean graph of the rows, NN-descent rounds in the fit's metric).",
                     TypeConverters.toString)
     build_kwds = _p("build_kwds", "kNN graph options, e.g. {'nlist': ..., 'nprobe': ..., 'probe': 'query' | 'list', "
                     "'nnd_iters': ...} for build_algo='ivf' / 'nn_descent'; {'proj_dim': ..., 'nnd_iters': ..., "
                     "'a': ..., 'b': ..., 'R': ...} (and 'nlist' / 'nprobe' / 'probe' for its dense candidate build) "
-                    "for build_algo='rp_nn_descent'.", TypeConverters.identity)
+                    "for build_algo='rp_nn_descent'; {'nnd_iters': ..., 'a': ..., 'b': ..., 'R': ..., 'cand_k': ...} (and "
+                    "'nlist' / 'nprobe' / 'probe' for its Euclidean candidate build) for build_algo='metric_nn_descent'.",
+                    TypeConverters.identity)
 
     def __init__(self) -> None:
         super().__init__()
