@@ -13,7 +13,7 @@ MI355X design (per rank = per item partition):
   the finished block is back at its owner. Per-rank memory is two query blocks + their top-k
   lists, instead of every rank's queries (the all-gather's O(Q·n) per rank);
 * exact: the fused MFMA distance + LDS top-k kernel (``srml_knn_f32``, k <= 64) or the distance
-  chunk + radix-select path (k <= 1024) over the local items, candidates refined exactly;
+  chunk + radix-select path (k <= ``ops.TOPK_KMAX`` = 16384) over the local items, candidates refined exactly;
 * IVF-Flat: coarse quantiser trained with the device KMeans kernels, items bucketed into
   contiguous inverted lists (device sort), probes chosen with the same top-k kernel against the
   centroids, lists scanned by ``srml_ivf_search_f32``; queries ride the same ring;
@@ -131,7 +131,7 @@ def _refine(Q: torch.Tensor, items: torch.Tensor, pos: torch.Tensor, metric: str
 
 
 def _resort(d: torch.Tensor, i: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    v, j = torch.sort(d, dim=1)
+    v, j = torch.sort(d, dim=1, stable=True)  # ties keep the candidate order, as ops.knn_refine_sort does
     return v, i.gather(1, j)
 
 

@@ -1829,7 +1829,7 @@ def topk_rows(vals: torch.Tensor, k: int, ids: Optional[torch.Tensor] = None, id
               slice_len: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """k smallest values of every row (ascending, ties -> lower column) and their ids
     (``ids[r, c]``, or ``id_base + c``). Rows longer than ``slice_len`` are selected per slice and
-    merged. Device: ``srml_topk_rows_f32``; host: torch.topk."""
+    merged. Signed zeros tie. Device: ``srml_topk_rows_f32``; host: a stable torch.sort."""
     rows, L = vals.shape
     if not vals.is_cuda:
         kk = min(k, L)
@@ -1867,8 +1867,9 @@ def topk_rows(vals: torch.Tensor, k: int, ids: Optional[torch.Tensor] = None, id
 def knn(Q: torch.Tensor, I: torch.Tensor, k: int, inorm: Optional[torch.Tensor] = None,
         qnorm: Optional[torch.Tensor] = None, id_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact k nearest items of every query: (squared L2 distances fp32 [mq, k], item ids int64 [mq, k]).
-    Device: k <= 64 -> fused MFMA tiles + LDS insertion lists (``srml_knn_f32``); 64 < k <= 1024 ->
-    bounded distance chunks on the MFMA tile + radix select (``_knn_large_k``)."""
+    Ties go to the lower item id on the device and on the host. Device: k <= 64 -> fused MFMA tiles
+    + LDS insertion lists (``srml_knn_f32``); 64 < k <= ``TOPK_KMAX`` (16384) -> bounded distance
+    chunks on the MFMA tile + radix select (``_knn_large_k``)."""
     mq, n = Q.shape
     mi = I.shape[0]
     kk = min(k, mi)
@@ -1886,9 +1887,9 @@ def knn(Q: torch.Tensor, I: torch.Tensor, k: int, inorm: Optional[torch.Tensor] 
         bs = max(1, (1 << 25) // max(mi, 1))
         for s in range(0, mq, bs):
             d = (qnorm[s: s + bs].float().view(-1, 1) + inorm.float().view(1, -1) - 2.0 * (Qf[s: s + bs] @ If.T))
-            v, i = torch.topk(d, kk, dim=1, largest=False)
+            v, i = topk_rows(d, kk, id_base=int(id_offset))  # stable: ties go to the lower id, as on the device
             outs_d.append(v.clamp_min(0))
-            outs_i.append(i + id_offset)
+            outs_i.append(i)
         return torch.cat(outs_d), torch.cat(outs_i)
     Q = _c(Q)
     I = _c(I.to(torch.float32))
@@ -1909,7 +1910,7 @@ def knn(Q: torch.Tensor, I: torch.Tensor, k: int, inorm: Optional[torch.Tensor] 
 
 def _knn_large_k(Q: torch.Tensor, I: torch.Tensor, k: int, inorm: Optional[torch.Tensor],
                  qnorm: Optional[torch.Tensor], id_offset: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """64 < k <= 1024: per (query chunk, item chunk) the partial distances ||i||^2 - 2 q.i are
+    """64 < k <= ``TOPK_KMAX``: per (query chunk, item chunk) the partial distances ||i||^2 - 2 q.i are
     materialised (<= 1 GB) by the MFMA tile kernel, selected per 64k-column slice by the radix-
     select kernel, and the per-chunk lists merged by the same kernel with ids."""
     mq, n = Q.shape

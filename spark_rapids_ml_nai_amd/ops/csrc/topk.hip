@@ -1,4 +1,4 @@
-// Large-k exact kNN (64 < k <= 1024) and the row-wise top-k selection shared with the k <= 64
+// Large-k exact kNN (64 < k <= TK_KMAX = 16384) and the row-wise top-k selection shared with the k <= 64
 // slice merge.
 //
 //  * srml_knn_dist_f32 — D[q][i] = ||i||^2 - 2 q.i for a (query chunk x item chunk) on the fp32
@@ -76,6 +76,13 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_w, int& total) {
   return base + x - v;
 }
 
+// Selection key of the radix select: `orderable` with -0.0 canonicalised to +0.0, so signed zeros
+// tie (and keep the lower column) as they do numerically and in the host form. Local to the select:
+// `orderable` itself is shared with the DBSCAN keys and stays a pure bit map.
+__device__ __forceinline__ unsigned select_key(float f) {
+  return orderable(__float_as_uint(f) == 0x80000000u ? 0.f : f);
+}
+
 __global__ __launch_bounds__(TK_T) void topk_rows_kernel(const float* __restrict__ vals, long ldv, long slice_len,
                                                          int L_total, const long long* __restrict__ ids, long ldid,
                                                          long long id_base, int k, float* __restrict__ out_v,
@@ -104,7 +111,7 @@ __global__ __launch_bounds__(TK_T) void topk_rows_kernel(const float* __restrict
       for (int i = t; i < 2048; i += TK_T) hist[i] = 0;
       __syncthreads();
       for (int i = t; i < L; i += TK_T) {
-        const unsigned key = orderable(v[i]);
+        const unsigned key = select_key(v[i]);
         if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & (nb - 1u)], 1);
       }
       __syncthreads();
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(TK_T) void topk_rows_kernel(const float* __restrict
   int run_lt = 0, run_eq = 0;
   for (int b0 = 0; b0 < L; b0 += TK_T) {
     const int i = b0 + t;
-    const unsigned key = i < L ? orderable(v[i]) : 0xffffffffu;
+    const unsigned key = i < L ? select_key(v[i]) : 0xffffffffu;
     const bool lt = i < L && (take_all || key < T);
     const bool eq = i < L && !take_all && key == T;
     int total;
