@@ -85,14 +85,17 @@ def _ivf_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarra
     import torch
 
     from .core.base import to_device
-    from .models.knn import (build_cagra, build_ivf, build_ivfpq, cagra_knn, check_cagra_args, check_pq_args,
-                             default_pq_m, exact_knn, ivf_knn, ivfpq_knn)
+    from .models.knn import (build_cagra, build_ivf, build_ivfpq, cagra_compression, cagra_knn, check_cagra_args,
+                             check_pq_args, default_pq_m, exact_knn, ivf_knn, ivfpq_knn)
 
     items, item_ids, queries, query_ids, k, metric, algorithm, nlist, nprobe, seed, cache = payload[:11]
     pq = payload[11] if len(payload) > 11 else None  # "ivfpq": (M, n_bits, refine_ratio); "cagra": _cagra_params
     n = _agree_ncols(ctx, items, queries)
+    comp = None  # "cagra" with compression: pq = _cagra_params' 8 values + (compression tuple, refine_ratio)
     if algorithm == "cagra":
         check_cagra_args(pq, k, metric)  # the same on every rank: all raise alike
+        if len(pq) > 8:
+            comp = cagra_compression(pq[8], n)  # pq_dim against the same n on every rank
     if algorithm == "ivfpq":
         M, n_bits, refine_ratio = pq
         M = int(M) if M is not None else default_pq_m(max(n, 1))
@@ -108,12 +111,16 @@ def _ivf_worker(ctx: WorkerContext, payload: Tuple[Any, ...]) -> Tuple[np.ndarra
         igd, gd, build_algo = pq[:3]
         if X.shape[0] > 0:
             key = ("cagra", int(igd), int(gd), build_algo, int(seed))  # build parameters only: a search-only
-            index = cache.get(key) if cache is not None else None      # parameter never forces a rebuild
+            if comp is not None:                                       # parameter never forces a rebuild
+                key += (comp,)
+            index = cache.get(key) if cache is not None else None
             if index is None or index.items.device != X.device:
-                index = build_cagra(X, ids, int(igd), int(gd), build_algo, seed)
+                index = build_cagra(X, ids, int(igd), int(gd), build_algo, seed) if comp is None else \
+                    build_cagra(X, ids, int(igd), int(gd), build_algo, seed, compression=comp)
                 if cache is not None:
                     cache[key] = index
-        d, i = cagra_knn(index, Q, k, tuple(pq[3:]) + (int(seed),), ctx, metric)
+        search = tuple(pq[3:8]) + (int(seed),) + ((int(pq[9]),) if comp is not None else ())
+        d, i = cagra_knn(index, Q, k, search, ctx, metric)
         return query_ids, i, d
     if algorithm == "ivfpq":
         if X.shape[0] > 0:
@@ -546,10 +553,43 @@ _CAGRA_BUILD_ALGOS = {"ivf_pq": "auto", "auto": "auto", "nn_descent": "nn_descen
 _CAGRA_METRICS = ("euclidean", "l2", "sqeuclidean")
 
 
-def _cagra_params(ap: Dict[str, Any]) -> Tuple[int, int, str, int, int, int, int, int]:
+_CAGRA_VQ_MAX = 1024  # ops.CAGRA_VQ_MAX
+_CAGRA_COMPRESSION = {"pq_bits": 8, "pq_dim": 0, "vq_n_centers": 0, "kmeans_n_iters": 25}
+
+
+def _cagra_compression(comp: Any) -> Optional[Tuple[int, int, int, int]]:
+    """(pq_bits, pq_dim, vq_n_centers, kmeans_n_iters) of ``algoParams["compression"]`` (cuVS names; 0 for
+    ``pq_dim`` / ``vq_n_centers`` selects the default where n and N are known), or None."""
+    if comp is None:
+        return None
+    if not isinstance(comp, dict):
+        raise ValueError("cagra: compression=%r must be None or a dict with the keys %s"
+                         % (comp, sorted(_CAGRA_COMPRESSION)))
+    unknown = sorted(set(comp) - set(_CAGRA_COMPRESSION))
+    if unknown:
+        raise ValueError("cagra: compression has unknown keys %s; expected %s" % (unknown, sorted(_CAGRA_COMPRESSION)))
+    out = {}
+    for name, default in _CAGRA_COMPRESSION.items():
+        v = comp.get(name, default)
+        if v is None or isinstance(v, (bool, str)) or int(v) != v:
+            raise ValueError("cagra: compression %s=%r must be an integer" % (name, v))
+        out[name] = int(v)
+    if not 4 <= out["pq_bits"] <= 8:
+        raise ValueError("cagra: compression pq_bits=%d outside 4..8" % out["pq_bits"])
+    if not 0 <= out["pq_dim"] <= _PQ_MMAX:
+        raise ValueError("cagra: compression pq_dim=%d outside 0..%d" % (out["pq_dim"], _PQ_MMAX))
+    if not 0 <= out["vq_n_centers"] <= _CAGRA_VQ_MAX:
+        raise ValueError("cagra: compression vq_n_centers=%d outside 0..%d" % (out["vq_n_centers"], _CAGRA_VQ_MAX))
+    if out["kmeans_n_iters"] < 1:
+        raise ValueError("cagra: compression kmeans_n_iters=%d must be >= 1" % out["kmeans_n_iters"])
+    return out["pq_bits"], out["pq_dim"], out["vq_n_centers"], out["kmeans_n_iters"]
+
+
+def _cagra_params(ap: Dict[str, Any]) -> Tuple[Any, ...]:
     """(intermediate_graph_degree, graph_degree, builder of ``build_knn_graph``, itopk_size rounded up to
     a multiple of 32, search_width, max_iterations, min_iterations, num_random_samplings) of
-    ``algoParams`` for ``"cagra"`` (cuVS names); the checks that need no feature count."""
+    ``algoParams`` for ``"cagra"`` (cuVS names), followed with ``compression`` by (the tuple of
+    ``_cagra_compression``, refine_ratio); the checks that need no feature count."""
     def as_int(name: str, default: int) -> int:
         v = ap.get(name, default)
         if v is None or isinstance(v, (bool, str)) or int(v) != v:
@@ -564,8 +604,7 @@ def _cagra_params(ap: Dict[str, Any]) -> Tuple[int, int, str, int, int, int, int
     algo = ap.get("build_algo", "ivf_pq")
     if not isinstance(algo, str) or algo.lower() not in _CAGRA_BUILD_ALGOS:
         raise ValueError("cagra: build_algo=%r not in %s" % (algo, sorted(_CAGRA_BUILD_ALGOS)))
-    if ap.get("compression") is not None:
-        raise ValueError("cagra: compression=%r is not supported (only None)" % (ap["compression"],))
+    comp = _cagra_compression(ap.get("compression"))
     itopk = as_int("itopk_size", 64)
     if not 1 <= itopk <= _CAGRA_ITOPK_MAX:
         raise ValueError("cagra: itopk_size=%d outside 1..%d" % (itopk, _CAGRA_ITOPK_MAX))
@@ -578,7 +617,13 @@ def _cagra_params(ap: Dict[str, Any]) -> Tuple[int, int, str, int, int, int, int
         raise ValueError("cagra: max_iterations=%d, min_iterations=%d, num_random_samplings=%d out of range"
                          % (max_it, min_it, nrs))
     as_int("seed", 1)
-    return igd, gd, _CAGRA_BUILD_ALGOS[algo.lower()], itopk, width, max_it, min_it, nrs
+    out = (igd, gd, _CAGRA_BUILD_ALGOS[algo.lower()], itopk, width, max_it, min_it, nrs)
+    if comp is None:
+        return out
+    refine_ratio = as_int("refine_ratio", 2)  # read with compression only
+    if refine_ratio < 1:
+        raise ValueError("cagra: refine_ratio=%d must be >= 1" % refine_ratio)
+    return out + (comp, refine_ratio)
 
 
 class ApproximateNearestNeighbors(ApproximateNearestNeighborsClass, _NoPersistence, _ANNParams):
@@ -589,6 +634,10 @@ class ApproximateNearestNeighbors(ApproximateNearestNeighborsClass, _NoPersisten
     ``algorithm="cagra"`` builds a fixed-degree graph per item partition and walks it greedily on the device
     (``algoParams``, cuVS names: ``intermediate_graph_degree``, ``graph_degree``, ``build_algo``, ``itopk_size``,
     ``search_width``, ``max_iterations``, ``min_iterations``, ``num_random_samplings``; Euclidean metrics only).
+    ``algoParams["compression"]`` (``None``, or a dict of ``pq_bits`` 4..8, ``pq_dim``, ``vq_n_centers`` <= 1024,
+    ``kmeans_n_iters``; cuVS VPQ) makes the walk score one-byte codes instead of the rows and re-scores
+    ``min(itopk_size, k * refine_ratio)`` candidates exactly (``refine_ratio`` default 2); it reduces the search's
+    memory traffic, not the index's size.
 
     >>> from spark_rapids_ml_nai_amd.knn import ApproximateNearestNeighbors
     >>> ann = ApproximateNearestNeighbors(k=2, algoParams={"nlist": 2, "nprobe": 2}, inputCol="features")

@@ -25,7 +25,9 @@ MI355X design (per rank = per item partition):
 * CAGRA (cuVS naming; the later releases of the reference ship it): per rank the all-points kNN
   graph of ``models/knn_graph.py``, cut to a fixed degree by rank-based detour pruning and merged
   with its reverse edges (``csrc/cagra.hip``), walked by ``srml_cagra_search_f32``: one workgroup
-  per query, the sorted candidate list, the visited hash and the query row in LDS.
+  per query, the sorted candidate list, the visited hash and the query row in LDS. With
+  ``compression`` (cuVS VPQ) the walk scores one-byte codes through per-query tables in LDS
+  (``srml_cagra_search_vpq_f32``) and ``k * refine_ratio`` of its candidates are re-scored exactly.
 """
 from __future__ import annotations
 
@@ -183,11 +185,11 @@ class IVFIndex:
     ids: torch.Tensor
 
 
-def build_ivf(X: torch.Tensor, ids: torch.Tensor, nlist: int, seed: int = 1, iters: int = 20,
-              train_rows_per_list: int = 256) -> IVFIndex:
-    """Coarse quantiser (Lloyd on a row subsample, as IVF trainers do) + contiguous inverted lists."""
+def train_coarse(X: torch.Tensor, nlist: int, seed: int = 1, iters: int = 20,
+                 train_rows_per_list: int = 256) -> torch.Tensor:
+    """Centres fp32 [nlist, n] of a coarse quantiser: Lloyd on a row subsample, as IVF trainers do
+    (1 <= nlist <= rows). The IVF lists and the vector quantiser of the compressed CAGRA index share it."""
     m = X.shape[0]
-    nlist = max(1, min(int(nlist), m))
     gen = torch.Generator().manual_seed(int(seed))
     ntrain = min(m, max(nlist * train_rows_per_list, 4 * nlist))
     T = X if ntrain == m else X.index_select(0, torch.randperm(m, generator=gen)[:ntrain].to(X.device))
@@ -198,6 +200,14 @@ def build_ivf(X: torch.Tensor, ids: torch.Tensor, nlist: int, seed: int = 1, ite
         lab = ops.nearest_list(T, C, FT, tn)
         sums, counts = ops.cluster_sums(T, lab, nlist)
         C = torch.where(counts.view(-1, 1) > 0, (sums / counts.clamp_min(1).double().view(-1, 1)).float(), C)
+    return C
+
+
+def build_ivf(X: torch.Tensor, ids: torch.Tensor, nlist: int, seed: int = 1, iters: int = 20,
+              train_rows_per_list: int = 256) -> IVFIndex:
+    """Coarse quantiser (``train_coarse``) + contiguous inverted lists."""
+    nlist = max(1, min(int(nlist), X.shape[0]))
+    C = train_coarse(X, nlist, seed, iters, train_rows_per_list)
     lab = ops.nearest_list(X, C, ops.quantizer_planes(X) if nlist > 256 else None)
     order, off, _ = ops.label_sort(lab, nlist)  # stable: rows keep their order inside a list
     order = order.long()
@@ -345,6 +355,12 @@ class CagraIndex:
     items: torch.Tensor   # [N, n] fp32, original order
     ids: torch.Tensor     # [N] int64
     graph: torch.Tensor   # [N, gd] int32, -1 padded at the tail
+    # VPQ compression (None without): the search scores these instead of gathering rows of ``items``
+    vq_centers: Optional[torch.Tensor] = None   # fp32 [nv, n]
+    vq_labels: Optional[torch.Tensor] = None    # int32 [N], original order
+    codebooks: Optional[torch.Tensor] = None    # fp32 [M, ksub, dsub] over residuals x - c_label
+    codes: Optional[torch.Tensor] = None        # uint8 [N, M], row-major, original order
+    xhat_sqnorm: Optional[torch.Tensor] = None  # fp32 [N]: ||c_label + codewords||^2
 
 
 def check_cagra_args(params: Tuple, k: int, metric: str) -> None:
@@ -356,12 +372,61 @@ def check_cagra_args(params: Tuple, k: int, metric: str) -> None:
         raise ValueError("cagra: k=%d exceeds itopk_size=%d" % (k, itopk))
 
 
+def cagra_compression(comp: Tuple[int, int, int, int], n: int) -> Tuple[int, int, int, int]:
+    """(pq_bits, pq_dim, vq_n_centers, kmeans_n_iters) with ``pq_dim = 0`` resolved to
+    ``default_pq_m(n)``; the checks that need the feature count (every rank raises alike)."""
+    pq_bits, pq_dim, nv, iters = (int(v) for v in comp)
+    pq_dim = pq_dim if pq_dim else default_pq_m(max(n, 1))
+    if pq_dim < 1 or pq_dim > ops.PQ_MMAX or n % pq_dim != 0:
+        raise ValueError("cagra: compression pq_dim=%d must divide the %d features and lie in 1..%d"
+                         % (pq_dim, n, ops.PQ_MMAX))
+    return pq_bits, pq_dim, nv, iters
+
+
+def compress_cagra(index: "CagraIndex", comp: Tuple[int, int, int, int], seed: int,
+                    train_rows_per_code: int = 64, pq_iters: int = 10) -> None:
+    """VPQ arrays of ``index.items`` in original order: vector quantiser (``train_coarse``), codebooks
+    over the residuals of ``build_ivfpq``'s row subsample (``train_pq``), the codes and ||x^||^2."""
+    X = index.items
+    N, n = X.shape
+    pq_bits, M, nv, iters = cagra_compression(comp, n)
+    ksub = 1 << pq_bits
+    nv = nv if nv else min(ops.CAGRA_VQ_MAX, max(1, int(round(N ** 0.5))))
+    nv = max(1, min(nv, N, ops.CAGRA_VQ_MAX))
+    C = train_coarse(X, nv, seed, iters).contiguous()
+    lab = ops.nearest_list(X, C, ops.quantizer_planes(X) if nv > 256 else None).int().contiguous()
+    ntrain = min(N, ksub * train_rows_per_code)
+    if ntrain < N:
+        gen = torch.Generator().manual_seed(int(seed) + 0x4956)
+        sel = torch.randperm(N, generator=gen)[:ntrain].to(X.device)
+        R = X.index_select(0, sel) - C.index_select(0, lab.index_select(0, sel).long())
+    else:
+        R = X - C.index_select(0, lab.long())
+    cb = train_pq(R, M, ksub, seed, pq_iters)
+    codes = ops.pq_encode(X, cb, C, lab)
+    xn = torch.empty(N, dtype=torch.float32, device=X.device)
+    cbd = cb.double()
+    marange = torch.arange(M, device=X.device).view(1, M)
+    step = max(1, (1 << 24) // max(1, n))
+    for s in range(0, N, step):  # build-time work: fp64, plain torch
+        xh = C.double().index_select(0, lab[s: s + step].long()) + cbd[marange, codes[s: s + step].long()].flatten(1)
+        xn[s: s + step] = (xh * xh).sum(1).float()
+    index.vq_centers, index.vq_labels, index.codebooks, index.codes, index.xhat_sqnorm = C, lab, cb, codes, xn
+
+
 def build_cagra(X: torch.Tensor, ids: torch.Tensor, igd: int, gd: int, build_algo: str = "auto", seed: int = 1,
-                phases: Optional[dict] = None) -> CagraIndex:
+                phases: Optional[dict] = None, compression: Optional[Tuple[int, int, int, int]] = None) -> CagraIndex:
     """The kNN graph of ``build_knn_graph`` at ``igd + 1`` neighbours without each row's own index
     (absent among duplicate rows: the last entry goes instead), detour-pruned to ``gd`` edges
     (``ops.cagra_prune``) and merged with its reverse edges (``ops.cagra_merge``). Both degrees are
-    clamped to N - 1. ``phases`` (seconds): "knn_graph", "prune", "merge"."""
+    clamped to N - 1. ``phases`` (seconds): "knn_graph", "prune", "merge", "compress".
+
+    ``compression = (pq_bits, pq_dim, vq_n_centers, kmeans_n_iters)`` (cuVS VPQ; 0 for ``pq_dim`` /
+    ``vq_n_centers``: ``default_pq_m(n)`` / ``min(1024, round(sqrt(N)))``) leaves the graph as it is,
+    built on the fp32 rows in original order, and adds the vector-quantiser centres and labels, the
+    product-quantiser codebooks over the residuals, the one-byte codes and ``||x^||^2`` to the index
+    for ``ops.cagra_search_vpq``. The index keeps ``items`` for the exact re-score, as ``IVFPQIndex``
+    does: compression here reduces the search's memory traffic, not the index's capacity."""
     import time
 
     from .knn_graph import build_knn_graph
@@ -371,7 +436,10 @@ def build_cagra(X: torch.Tensor, ids: torch.Tensor, igd: int, gd: int, build_alg
     igd = max(0, min(int(igd), N - 1))
     gd = min(int(gd), igd)
     if gd < 1:  # one row: no edge to give
-        return CagraIndex(Xf, ids, torch.full((N, 1), -1, dtype=torch.int32, device=X.device))
+        index = CagraIndex(Xf, ids, torch.full((N, 1), -1, dtype=torch.int32, device=X.device))
+        if compression is not None and N > 0:
+            compress_cagra(index, compression, seed)
+        return index
 
     def lap(name: str, t0: float) -> float:
         if phases is not None:
@@ -391,26 +459,42 @@ def build_cagra(X: torch.Tensor, ids: torch.Tensor, igd: int, gd: int, build_alg
     P = ops.cagra_prune(G, gd)
     t0 = lap("prune", t0)
     F = ops.cagra_merge(P, gd)
-    lap("merge", t0)
-    return CagraIndex(Xf, ids, F)
+    t0 = lap("merge", t0)
+    index = CagraIndex(Xf, ids, F)
+    if compression is not None:
+        compress_cagra(index, compression, seed)
+        lap("compress", t0)
+    return index
 
 
 def cagra_knn(index: Optional[CagraIndex], queries: torch.Tensor, k: int, params: Tuple, ctx: WorkerContext,
               metric: str = "euclidean") -> Tuple[np.ndarray, np.ndarray]:
     """Beam search of this rank's graph (``ops.cagra_search``) for the k best of the list, re-scored
     exactly; queries ride the ring as for IVF-Flat. ``params`` = (itopk_size, search_width,
-    max_iterations, min_iterations, num_random_samplings, seed)."""
-    itopk, width, max_iter, min_iter, nrs, seed = (int(v) for v in params)
+    max_iterations, min_iterations, num_random_samplings, seed[, refine_ratio]). On a compressed index
+    the walk scores the codes (``ops.cagra_search_vpq``), ``kc = min(itopk_size, k * refine_ratio)`` of
+    its list are re-scored on the rows and k kept."""
+    itopk, width, max_iter, min_iter, nrs, seed = (int(v) for v in params[:6])
+    refine_ratio = int(params[6]) if len(params) > 6 else 2
     if k > itopk:
         raise ValueError("cagra: k=%d exceeds itopk_size=%d" % (k, itopk))
+    if refine_ratio < 1:
+        raise ValueError("cagra: refine_ratio=%d must be >= 1" % refine_ratio)
     S = min(itopk * nrs, ops.CAGRA_SEED_MAX)
+    kc = min(itopk, int(k) * refine_ratio)
 
     def local(Q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         if index is None:
             return (torch.full((Q.shape[0], k), float("inf"), device=Q.device),
                     torch.full((Q.shape[0], k), -1, dtype=torch.int64, device=Q.device))
-        _, pos = ops.cagra_search(Q, index.items, index.graph, k, itopk, width, max_iter, min_iter, S, seed)
-        d, pos = _refine_sorted(Q, index.items, pos, metric)
+        if index.codes is not None:
+            _, pos = ops.cagra_search_vpq(Q, index.vq_centers, index.vq_labels, index.codebooks, index.codes,
+                                          index.xhat_sqnorm, index.graph, kc, itopk, width, max_iter, min_iter, S, seed)
+            d, pos = _refine_sorted(Q, index.items, pos, metric)
+            d, pos = d[:, :k], pos[:, :k]
+        else:
+            _, pos = ops.cagra_search(Q, index.items, index.graph, k, itopk, width, max_iter, min_iter, S, seed)
+            d, pos = _refine_sorted(Q, index.items, pos, metric)
         gi = torch.where(pos >= 0, index.ids[pos.clamp_min(0)], torch.full_like(pos, -1))
         return _pad_k(d, gi, k)
 

@@ -2335,6 +2335,7 @@ CAGRA_ITOPK_MAX = 512
 CAGRA_CAND_MAX = 512    # search_width * graph_degree
 CAGRA_SEED_MAX = 1024
 CAGRA_LDS_TOTAL = 160 * 1024
+CAGRA_VQ_MAX = 1024     # vector-quantiser centres of the VPQ search: nv * n FMAs per query build its B table
 _CAGRA_EMPTY = (1 << 63) - 1  # the empty key of the host path (int64; the device's is all ones)
 
 
@@ -2355,17 +2356,30 @@ def cagra_lds_bytes(n: int, itopk: int, width: int, gd: int, S: int, max_iter: i
     return ((n + 3) // 4) * 16 + pmax * 8 + max(c_init, c_iter) * 4 + ((width + 3) // 4) * 16 + slots * 4 + 64
 
 
-def cagra_auto_iters(n: int, itopk: int, width: int, gd: int, S: int) -> int:
-    """``max_iterations = 0``: itopk / width + 16, lowered to what the kernel's LDS holds (>= 1)."""
+def cagra_vpq_lds_bytes(n: int, itopk: int, width: int, gd: int, S: int, max_iter: int, M: int, ksub: int,
+                        nv: int) -> int:
+    """LDS bytes of one ``srml_cagra_search_vpq_f32`` workgroup (``srml_cagra_vpq_lds_bytes``):
+    ``cagra_lds_bytes`` plus the table T (M * ksub floats) and the centre dots B (nv floats) behind the
+    query row, each padded to 16 bytes."""
+    return cagra_lds_bytes(n, itopk, width, gd, S, max_iter) + ((M * ksub + 3) // 4) * 16 + ((nv + 3) // 4) * 16
+
+
+def cagra_auto_iters(n: int, itopk: int, width: int, gd: int, S: int,
+                     vpq: Optional[Tuple[int, int, int]] = None) -> int:
+    """``max_iterations = 0``: itopk / width + 16, lowered to what the kernel's LDS holds (>= 1).
+    ``vpq = (M, ksub, nv)`` budgets against the layout of the VPQ search."""
+    extra = cagra_vpq_lds_bytes(n, itopk, width, gd, S, 0, *vpq) - cagra_lds_bytes(n, itopk, width, gd, S, 0) if vpq \
+        else 0
     it = itopk // width + 16
-    while it > 1 and cagra_lds_bytes(n, itopk, width, gd, S, it) > CAGRA_LDS_TOTAL:
+    while it > 1 and cagra_lds_bytes(n, itopk, width, gd, S, it) + extra > CAGRA_LDS_TOTAL:
         it -= 1
     return it
 
 
-def _cagra_check(n: int, gd: int, k: int, itopk: int, width: int, max_iter: int, min_iter: int, S: int) -> int:
-    """The limits of ``cagra_search`` (both paths raise alike, nothing is launched); returns the
-    resolved ``max_iter``."""
+def _cagra_check(n: int, gd: int, k: int, itopk: int, width: int, max_iter: int, min_iter: int, S: int,
+                 vpq: Optional[Tuple[int, int, int]] = None) -> int:
+    """The limits of ``cagra_search`` / ``cagra_search_vpq`` (both paths raise alike, nothing is
+    launched); returns the resolved ``max_iter``."""
     if itopk < 32 or itopk > CAGRA_ITOPK_MAX or itopk % 32:
         raise ValueError("cagra_search: itopk=%d must be a multiple of 32 in 32..%d" % (itopk, CAGRA_ITOPK_MAX))
     if gd < 1 or gd > CAGRA_DMAX:
@@ -2379,7 +2393,15 @@ def _cagra_check(n: int, gd: int, k: int, itopk: int, width: int, max_iter: int,
     if max_iter < 0 or max_iter > 65536 or min_iter < 0:
         raise ValueError("cagra_search: max_iter=%d / min_iter=%d out of range" % (max_iter, min_iter))
     if max_iter == 0:
-        max_iter = cagra_auto_iters(n, itopk, width, gd, S)
+        max_iter = cagra_auto_iters(n, itopk, width, gd, S, vpq)
+    if vpq is not None:
+        need = cagra_vpq_lds_bytes(n, itopk, width, gd, S, max_iter, *vpq)
+        if need > CAGRA_LDS_TOTAL:
+            raise ValueError("cagra_search_vpq: n=%d, M=%d, ksub=%d, %d centres, itopk=%d, width=%d, graph degree=%d, "
+                             "seeds=%d, max_iter=%d need %d bytes of LDS (table of %d bytes and visited table "
+                             "included), past the %d of a CU" % ((n,) + tuple(vpq) + (itopk, width, gd, S, max_iter, need,
+                                                                                     vpq[0] * vpq[1] * 4, CAGRA_LDS_TOTAL)))
+        return max_iter
     need = cagra_lds_bytes(n, itopk, width, gd, S, max_iter)
     if need > CAGRA_LDS_TOTAL:
         raise ValueError("cagra_search: n=%d, itopk=%d, width=%d, graph degree=%d, seeds=%d, max_iter=%d need %d "
@@ -2524,13 +2546,16 @@ def cagra_merge(P: torch.Tensor, gd: int) -> torch.Tensor:
     return F
 
 
-def _cagra_search_host(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, seeds: torch.Tensor, k: int, itopk: int,
-                       width: int, max_iter: int, min_iter: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def _cagra_search_host(Q: torch.Tensor, N: int, F: torch.Tensor, seeds: torch.Tensor, k: int, itopk: int, width: int,
+                       max_iter: int, min_iter: int,
+                       scorer: Callable[[torch.Tensor], Callable[[torch.Tensor], torch.Tensor]]
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
     """The search rule of ``cagra_search`` in torch, all queries of a chunk in step. A key is
-    (fp32 bits of d2) << 32 | id << 1 | expanded, as on the device."""
+    (fp32 bits of d2) << 32 | id << 1 | expanded, as on the device. ``scorer(Qc)`` gives the chunk's
+    distance expression: candidate positions int64 [m, c] (>= 0) -> non-negative fp32 [m, c]."""
     nq, n = Q.shape
-    N, gd = int(X.shape[0]), int(F.shape[1])
-    Xf, Fl = X.float(), F.long()
+    gd = int(F.shape[1])
+    Fl = F.long()
     od = torch.full((nq, k), float("inf"), dtype=torch.float32)
     oi = torch.full((nq, k), -1, dtype=torch.int64)
     step = max(1, min(nq, (1 << 25) // max(1, N), (1 << 25) // max(1, max(width * gd, seeds.shape[1]) * n)))
@@ -2540,6 +2565,7 @@ def _cagra_search_host(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, seeds:
         rows = torch.arange(m).view(m, 1)
         visited = torch.zeros((m, N), dtype=torch.bool)
         keys = torch.full((m, itopk), _CAGRA_EMPTY, dtype=torch.int64)
+        score = scorer(Qc)
 
         def merge(keys: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
             cand = torch.where((cand >= 0) & (cand < N), cand, torch.full_like(cand, -1))
@@ -2549,7 +2575,7 @@ def _cagra_search_host(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, seeds:
             first = torch.ones_like(dup).scatter_(1, order, ~dup)
             new = (cand >= 0) & first & ~visited[rows, cand.clamp_min(0)]
             visited[rows.expand_as(cand)[new], cand[new]] = True
-            d2 = ((Xf[cand.clamp_min(0)] - Qc.unsqueeze(1)) ** 2).sum(-1)
+            d2 = score(cand.clamp_min(0))
             ck = (d2.contiguous().view(torch.int32).long() << 32) | (cand << 1)
             ck = torch.where(new, ck, torch.full_like(ck, _CAGRA_EMPTY))
             return torch.sort(torch.cat([keys, ck], 1), dim=1)[0][:, :itopk]
@@ -2604,7 +2630,9 @@ def cagra_search(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, k: int, itop
         return od, oi
     seeds = cagra_seeds(Q, N, S, seed)
     if not Q.is_cuda:
-        return _cagra_search_host(Q, X, F, seeds, int(k), int(itopk), int(width), max_iter, int(min_iter))
+        Xf = X.float()
+        return _cagra_search_host(Q, N, F, seeds, int(k), int(itopk), int(width), max_iter, int(min_iter),
+                                  lambda Qc: lambda cand: ((Xf[cand] - Qc.unsqueeze(1)) ** 2).sum(-1))
     Qc = Q if Q.dtype == torch.float32 and Q.stride(1) == 1 else _c(Q.float())
     Xc = X if X.dtype == torch.float32 and X.stride(1) == 1 else _c(X.float())
     Fc = _c(F)
@@ -2616,6 +2644,83 @@ def cagra_search(Q: torch.Tensor, X: torch.Tensor, F: torch.Tensor, k: int, itop
                          "the kernel's LDS" % (n, itopk, width, gd, S, max_iter))
     if rc != 0:
         raise RuntimeError("srml_cagra_search_f32 failed with status %d" % rc)
+    return od, oi
+
+
+def cagra_search_vpq(Q: torch.Tensor, vq_centers: torch.Tensor, vq_labels: torch.Tensor, codebooks: torch.Tensor,
+                     codes: torch.Tensor, xhat_sqnorm: torch.Tensor, F: torch.Tensor, k: int, itopk: int = 64,
+                     width: int = 1, max_iter: int = 0, min_iter: int = 0, S: int = 64, seed: int = 1
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``cagra_search`` over VPQ-compressed items: (keys fp32 [nq, k] ascending, row positions int64
+    [nq, k]; empty slots +inf / -1). Item i is ``x^_i = vq_centers[vq_labels[i]] + (codebooks[m,
+    codes[i, m]])_m`` (centres fp32 [nv, n], nv <= ``CAGRA_VQ_MAX``; labels int32 [N]; codebooks fp32
+    [M, ksub, n / M]; codes uint8 [N, M], a code >= ksub reads the last codeword) and
+    ``xhat_sqnorm[i] = ||x^_i||^2``. The rule is ``cagra_search``'s with, in place of d2, the fp32 key
+
+        max(0, ||q||^2 + xhat_sqnorm[i] - 2 (q . c_label_i + sum_m q_m . codebooks[m, codes[i, m]]))
+
+    i.e. ``||q - x^_i||^2`` expanded: a ranking key, to be re-scored on the rows. Device:
+    ``srml_cagra_search_vpq_f32`` with the per-query tables of the dots in LDS
+    (``cagra_vpq_lds_bytes``; past 160 KiB: ValueError); host: torch."""
+    nq, n = Q.shape
+    M, ksub, dsub = _pq_shapes(n, codebooks)
+    N = int(codes.shape[0])
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != M:
+        raise ValueError("cagra_search_vpq: codes must be uint8 [N, %d], got %s %s" % (M, codes.dtype, tuple(codes.shape)))
+    if vq_centers.dim() != 2 or vq_centers.shape[1] != n or not vq_centers.is_floating_point():
+        raise ValueError("cagra_search_vpq: centres %s do not match %d query features" % (tuple(vq_centers.shape), n))
+    nv = int(vq_centers.shape[0])
+    if not 1 <= nv <= CAGRA_VQ_MAX:
+        raise ValueError("cagra_search_vpq: %d vector-quantiser centres outside 1..%d" % (nv, CAGRA_VQ_MAX))
+    if vq_labels.dtype != torch.int32 or tuple(vq_labels.shape) != (N,):
+        raise ValueError("cagra_search_vpq: labels must be int32 [%d], got %s %s"
+                         % (N, vq_labels.dtype, tuple(vq_labels.shape)))
+    if xhat_sqnorm.dtype != torch.float32 or tuple(xhat_sqnorm.shape) != (N,):
+        raise ValueError("cagra_search_vpq: xhat_sqnorm must be fp32 [%d], got %s %s"
+                         % (N, xhat_sqnorm.dtype, tuple(xhat_sqnorm.shape)))
+    if F.dim() != 2 or F.dtype != torch.int32 or F.shape[0] != N:
+        raise ValueError("cagra_search_vpq: the graph must be int32 [%d, gd], got %s %s" % (N, F.dtype, tuple(F.shape)))
+    gd = int(F.shape[1])
+    max_iter = _cagra_check(n, gd, int(k), int(itopk), int(width), int(max_iter), int(min_iter), int(S), (M, ksub, nv))
+    od = torch.full((nq, k), float("inf"), dtype=torch.float32, device=Q.device)
+    oi = torch.full((nq, k), -1, dtype=torch.int64, device=Q.device)
+    if nq == 0 or N == 0:
+        return od, oi
+    seeds = cagra_seeds(Q, N, S, seed)
+    if not Q.is_cuda:
+        cb, Cf = codebooks.float(), vq_centers.float()
+        lab = vq_labels.long().clamp(0, nv - 1)
+        cd = codes.long().clamp_max(ksub - 1)
+
+        def scorer(Qc: torch.Tensor) -> Callable[[torch.Tensor], torch.Tensor]:
+            m = Qc.shape[0]
+            T = torch.einsum("qmd,mjd->qmj", Qc.view(m, M, dsub), cb)  # [m, M, ksub]
+            B = Qc @ Cf.t()
+            qn = (Qc * Qc).sum(1, keepdim=True)
+
+            def score(cand: torch.Tensor) -> torch.Tensor:
+                s = B.gather(1, lab[cand]) + T.gather(2, cd[cand].transpose(1, 2)).sum(1)
+                key = (qn + xhat_sqnorm[cand]) - 2.0 * s
+                return torch.where(key > 0, key, torch.zeros_like(key))
+
+            return score
+
+        return _cagra_search_host(Q, N, F, seeds, int(k), int(itopk), int(width), max_iter, int(min_iter), scorer)
+    Qc = Q if Q.dtype == torch.float32 and Q.stride(1) == 1 else _c(Q.float())
+    Cc = _c(vq_centers.float())
+    cbT = codebooks.float().transpose(1, 2).contiguous()  # [M, dsub, ksub]: lanes read over j
+    lab, xn, Fc = _c(vq_labels), _c(xhat_sqnorm), _c(F)
+    cdc = codes if codes.stride(1) == 1 and codes.stride(0) == M else codes.contiguous()
+    rc = native.call_status("srml_cagra_search_vpq_f32", Qc.data_ptr(), nq, n, Qc.stride(0), Cc.data_ptr(), nv,
+                            lab.data_ptr(), cbT.data_ptr(), cdc.data_ptr(), xn.data_ptr(), M, ksub, N, Fc.data_ptr(), gd,
+                            seeds.data_ptr(), int(S), int(k), int(itopk), int(width), max_iter, int(min_iter),
+                            od.data_ptr(), oi.data_ptr(), native.stream(Q.device))
+    if rc == -9:
+        raise ValueError("cagra_search_vpq: n=%d, M=%d, ksub=%d, %d centres, itopk=%d, width=%d, graph degree=%d, "
+                         "seeds=%d, max_iter=%d do not fit the kernel's LDS"
+                         % (n, M, ksub, nv, itopk, width, gd, S, max_iter))
+    if rc != 0:
+        raise RuntimeError("srml_cagra_search_vpq_f32 failed with status %d" % rc)
     return od, oi
 
 

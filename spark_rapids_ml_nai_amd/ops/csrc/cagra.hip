@@ -15,7 +15,25 @@
 //
 // A packed key is d2's fp32 bit pattern (non-negative, so it orders as an unsigned integer) in the
 // high word and (id << 1 | expanded) in the low word; all ones is the empty slot.
+//
+// Search on VPQ codes (srml_cagra_search_vpq_f32; cuVS "compression"): the same walk, one kernel
+// template, with the gather of 4 n bytes per candidate replaced by M + 8 bytes. Item i is a
+// vector-quantiser label and M one-byte codes, x^_i = c_label + (cb[m][code_im])_m, and its key is
+//   ||q||^2 + ||x^_i||^2 - 2 (B[label_i] + sum_m T[m][code_im]),  clamped at 0,
+// with T[m][j] = q_m . cb[m][j] (M x ksub floats) and B[l] = q . c_l (nv floats) built once per
+// query into LDS behind the query row: T as the inner-product table of the IVF-PQ scan (pq_lut.h),
+// B by the 8-lane teams that gather rows in the fp32 search (16-byte loads over the centre rows),
+// ||q||^2 by wave 0. A candidate keeps its team of 8 lanes: at the shape this is built for
+// (n = 128, M = 32) the code row is one 32-bit load per lane and one 32-byte sector per team, the
+// 4 lookups of a lane hit T in 4 different sub-tables, and width * gd = 64 candidates fill the 32
+// teams of the block twice; one candidate per lane would leave 7 of 8 lanes idle behind M serial
+// lookups. Each lane takes a contiguous slice of ceil(M / 4 / 8) code words (bytes when M % 4 != 0
+// or the codes are not 4-byte aligned), so M = 64 and 128 stay one run of 8 or 16 bytes per lane
+// and M < 32 leaves the upper lanes of a team without work; the DPP fold is the fp32 one. Lane 0
+// of the team fetches the label and ||x^_i||^2 beside the codes and packs the key.
 #include "common.h"
+
+#include "pq_lut.h"
 
 namespace {
 constexpr int CG_T = 256;
@@ -23,7 +41,11 @@ constexpr int CG_DMAX = 128;       // intermediate and final graph degree
 constexpr int CG_ITOPK_MAX = 512;
 constexpr int CG_CAND_MAX = 512;   // width * gd
 constexpr int CG_SEED_MAX = 1024;
-constexpr int CG_TEAM = 8;         // lanes per gathered row
+constexpr int CG_TEAM = 8;         // lanes per gathered row / per code row
+constexpr int CG_VQ_MAX = 1024;    // vector-quantiser centres: nv * n FMAs per query build B
+constexpr int CG_MMAX = 128;       // as PQ_MMAX / PQ_KSUBMAX of ivfpq.hip
+constexpr int CG_KSUBMAX = 256;
+static_assert(srml_pq::PQ_T == CG_T, "pq_build_lut strides by the block size of the search");
 static_assert(CG_TEAM == 8, "cg_score folds a team with the DPP steps of an 8-lane half row");
 constexpr size_t CG_STATIC_LDS = 64;
 constexpr size_t CG_LDS_TOTAL = 160 * 1024;  // per CU on gfx950; one workgroup may take all of it
@@ -46,13 +68,15 @@ __host__ __device__ inline unsigned cg_mix(unsigned h) {  // murmur3's finaliser
 }
 
 // The one place the dynamic LDS of the search kernel is laid out (host: the budget; device: the
-// pointers): query row | keys (list + candidates) | candidate ids | parents | visited table.
+// pointers): query row | T | B | keys (list + candidates) | candidate ids | parents | visited table.
+// T (M * ksub floats) and B (nv floats) exist for the VPQ search only; both are padded to 16 bytes.
 struct CgLayout {
   int c_init, c_iter, p_init, p_iter, lg_slots;
-  size_t q, buf, cand, par, vis, total;
+  size_t q, tab, bias, buf, cand, par, vis, total;
 };
 
-__host__ __device__ inline CgLayout cg_layout(int n, int itopk, int width, int gd, int S, int max_iter) {
+__host__ __device__ inline CgLayout cg_layout(int n, int itopk, int width, int gd, int S, int max_iter, int M = 0,
+                                              int ksub = 0, int nv = 0) {
   CgLayout L;
   L.c_init = cg_pow2(S);
   L.c_iter = cg_pow2((long)width * gd);
@@ -64,7 +88,9 @@ __host__ __device__ inline CgLayout cg_layout(int n, int itopk, int width, int g
   const int pmax = L.p_init > L.p_iter ? L.p_init : L.p_iter;
   const int cmax = L.c_init > L.c_iter ? L.c_init : L.c_iter;
   L.q = 0;
-  L.buf = L.q + (size_t)((n + 3) / 4) * 16;
+  L.tab = L.q + (size_t)((n + 3) / 4) * 16;
+  L.bias = L.tab + (size_t)(((long)M * ksub + 3) / 4) * 16;
+  L.buf = L.bias + (size_t)((nv + 3) / 4) * 16;
   L.cand = L.buf + (size_t)pmax * 8;
   L.par = L.cand + (size_t)cmax * 4;
   L.vis = L.par + (size_t)((width + 3) / 4) * 16;
@@ -238,63 +264,161 @@ __device__ __forceinline__ bool cg_visit(int* vis, int lg, int id) {
   return false;
 }
 
+// What a candidate is scored from: the fp32 rows, or the VPQ arrays with the query's tables in LDS.
+struct CgScore {
+  const float* qs;  // query row in LDS
+  // fp32
+  const float* X;
+  long ldx;
+  int n, vec;
+  // VPQ
+  const unsigned char* codes;  // [N, M]
+  const int* labels;           // [N]
+  const float* xn;             // [N] ||x^||^2
+  const float* T;              // LDS [M, ksub]
+  const float* B;              // LDS [nv]
+  float qn;
+  int M, ksub, nv, cvec;
+};
+
+__device__ __forceinline__ float cg_team_sum(float acc) {
+  acc += dpp_f<0xb1>(acc);   // quad_perm [1,0,3,2]
+  acc += dpp_f<0x4e>(acc);   // quad_perm [2,3,0,1]
+  acc += dpp_f<0x141>(acc);  // row_half_mirror: every lane of the team holds its 8-lane sum
+  return acc;
+}
+
 // Keys of the candidates cand[0, C) (-1: none) into dst[0, C). A team of 8 lanes takes one row:
 // 16-byte loads when the rows allow it (vec), 8 rows in flight per wave, all four waves.
-__device__ void cg_score(const float* qs, const float* __restrict__ X, long ldx, int n, int vec, const int* cand,
-                         int C, u64* dst) {
+template <bool VPQ>
+__device__ void cg_score(const CgScore& sc, const int* cand, int C, u64* dst) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g = lane / CG_TEAM, sub = lane % CG_TEAM;
-  const int n4 = vec ? (n >> 2) : 0;
-  for (int c0 = wid * (64 / CG_TEAM); c0 < C; c0 += 4 * (64 / CG_TEAM)) {  // wave-uniform
-    const int ci = c0 + g;
-    const int id = ci < C ? cand[ci] : -1;
-    float acc = 0.f;
-    if (id >= 0) {
-      const float* row = X + (long)id * ldx;
-      const floatx4* r4 = reinterpret_cast<const floatx4*>(row);
-      const floatx4* q4 = reinterpret_cast<const floatx4*>(qs);
-#pragma unroll 4
-      for (int c = sub; c < n4; c += CG_TEAM) {
-        const floatx4 x = r4[c], y = q4[c];
-        const float d0 = y.x - x.x, d1 = y.y - x.y, d2 = y.z - x.z, d3 = y.w - x.w;
-        acc = fmaf(d0, d0, acc);
-        acc = fmaf(d1, d1, acc);
-        acc = fmaf(d2, d2, acc);
-        acc = fmaf(d3, d3, acc);
+  if constexpr (VPQ) {
+    // this lane's slice of a code row: words (4 codes) on the vector path, bytes otherwise
+    const int M = sc.M, unit = sc.cvec ? 4 : 1, units = M / unit;
+    const int per = (units + CG_TEAM - 1) / CG_TEAM;
+    const int m0 = min(sub * per, units) * unit, m1 = min((sub + 1) * per, units) * unit;
+    const float* Tm = sc.T + m0 * sc.ksub;
+    for (int c0 = wid * (64 / CG_TEAM); c0 < C; c0 += 4 * (64 / CG_TEAM)) {  // wave-uniform
+      const int ci = c0 + g;
+      const int id = ci < C ? cand[ci] : -1;
+      float acc = 0.f, xn = 0.f;
+      int lab = 0;
+      if (id >= 0) {
+        if (sub == 0) {
+          lab = sc.labels[id];
+          xn = sc.xn[id];
+        }
+        if (m1 > m0) acc = srml_pq::pq_item_sum(sc.codes + (long)id * M + m0, Tm, m1 - m0, sc.ksub, sc.cvec != 0);
       }
-      for (int d = (n4 << 2) + sub; d < n; d += CG_TEAM) {
-        const float df = qs[d] - row[d];
-        acc = fmaf(df, df, acc);
+      acc = cg_team_sum(acc);
+      if (sub == 0 && ci < C) {
+        u64 key = CG_EMPTY;
+        if (id >= 0) {
+          const float s = sc.B[min(max(lab, 0), sc.nv - 1)] + acc;
+          const float d = fmaf(-2.f, s, sc.qn + xn);
+          key = ((u64)__float_as_uint(d > 0.f ? d : 0.f) << 32) | ((unsigned)id << 1);
+        }
+        dst[ci] = key;
       }
     }
-    acc += dpp_f<0xb1>(acc);   // quad_perm [1,0,3,2]
-    acc += dpp_f<0x4e>(acc);   // quad_perm [2,3,0,1]
-    acc += dpp_f<0x141>(acc);  // row_half_mirror: every lane of the team holds its 8-lane sum
-    if (sub == 0 && ci < C)
-      dst[ci] = id >= 0 ? (((u64)__float_as_uint(acc) << 32) | ((unsigned)id << 1)) : CG_EMPTY;
+  } else {
+    const float* qs = sc.qs;
+    const float* __restrict__ X = sc.X;
+    const long ldx = sc.ldx;
+    const int n = sc.n;
+    const int n4 = sc.vec ? (n >> 2) : 0;
+    for (int c0 = wid * (64 / CG_TEAM); c0 < C; c0 += 4 * (64 / CG_TEAM)) {  // wave-uniform
+      const int ci = c0 + g;
+      const int id = ci < C ? cand[ci] : -1;
+      float acc = 0.f;
+      if (id >= 0) {
+        const float* row = X + (long)id * ldx;
+        const floatx4* r4 = reinterpret_cast<const floatx4*>(row);
+        const floatx4* q4 = reinterpret_cast<const floatx4*>(qs);
+#pragma unroll 4
+        for (int c = sub; c < n4; c += CG_TEAM) {
+          const floatx4 x = r4[c], y = q4[c];
+          const float d0 = y.x - x.x, d1 = y.y - x.y, d2 = y.z - x.z, d3 = y.w - x.w;
+          acc = fmaf(d0, d0, acc);
+          acc = fmaf(d1, d1, acc);
+          acc = fmaf(d2, d2, acc);
+          acc = fmaf(d3, d3, acc);
+        }
+        for (int d = (n4 << 2) + sub; d < n; d += CG_TEAM) {
+          const float df = qs[d] - row[d];
+          acc = fmaf(df, df, acc);
+        }
+      }
+      acc = cg_team_sum(acc);
+      if (sub == 0 && ci < C)
+        dst[ci] = id >= 0 ? (((u64)__float_as_uint(acc) << 32) | ((unsigned)id << 1)) : CG_EMPTY;
+    }
   }
 }
 
 // Score cand[0, C), sort the keys (descending, at the end of buf[0, P)) and merge them into the
 // ascending list buf[0, itopk); the slots between stay empty, so buf[0, P) is bitonic.
-__device__ void cg_round(const float* qs, const float* __restrict__ X, long ldx, int n, int vec, const int* cand,
-                         int C, u64* buf, int P, int itopk) {
+template <bool VPQ>
+__device__ void cg_round(const CgScore& sc, const int* cand, int C, u64* buf, int P, int itopk) {
   for (int i = itopk + threadIdx.x; i < P - C; i += CG_T) buf[i] = CG_EMPTY;
-  cg_score(qs, X, ldx, n, vec, cand, C, buf + (P - C));
+  cg_score<VPQ>(sc, cand, C, buf + (P - C));
   __syncthreads();
   cg_sort_desc(buf + (P - C), C);
   cg_merge_asc(buf, P);
 }
 
+// The VPQ arrays of a search (unused by the fp32 instantiation).
+struct CgVpqArgs {
+  const float* centers;  // [nv, n]
+  const int* labels;
+  const float* cbT;      // [M, dsub, ksub]
+  const unsigned char* codes;
+  const float* xn;
+  int nv, M, ksub, cvec, bvec;  // cvec: 32-bit code loads; bvec: 16-byte centre loads
+};
+
+// B[l] = q . c_l for the nv centres: a team of 8 lanes per centre row, as cg_score gathers rows.
+__device__ void cg_center_dots(const float* qs, const float* __restrict__ Cn, int nv, int n, int vec, float* B) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int g = lane / CG_TEAM, sub = lane % CG_TEAM;
+  const int n4 = vec ? (n >> 2) : 0;
+  for (int l0 = wid * (64 / CG_TEAM); l0 < nv; l0 += 4 * (64 / CG_TEAM)) {  // wave-uniform
+    const int l = l0 + g;
+    float acc = 0.f;
+    if (l < nv) {
+      const float* row = Cn + (long)l * n;
+      const floatx4* r4 = reinterpret_cast<const floatx4*>(row);
+      const floatx4* q4 = reinterpret_cast<const floatx4*>(qs);
+#pragma unroll 4
+      for (int c = sub; c < n4; c += CG_TEAM) {
+        const floatx4 x = r4[c], y = q4[c];
+        acc = fmaf(y.x, x.x, acc);
+        acc = fmaf(y.y, x.y, acc);
+        acc = fmaf(y.z, x.z, acc);
+        acc = fmaf(y.w, x.w, acc);
+      }
+      for (int d = (n4 << 2) + sub; d < n; d += CG_TEAM) acc = fmaf(qs[d], row[d], acc);
+    }
+    acc = cg_team_sum(acc);
+    if (sub == 0 && l < nv) B[l] = acc;
+  }
+}
+
+template <bool VPQ>
 __global__ __launch_bounds__(CG_T) void cagra_search_kernel(const float* __restrict__ Q, int n, long ldq,
                                                             const float* __restrict__ X, long N, long ldx,
                                                             const int* __restrict__ F, int gd,
                                                             const int* __restrict__ seeds, int S, int k, int itopk,
                                                             int width, int max_iter, int min_iter, int vec,
-                                                            float* __restrict__ out_d, long long* __restrict__ out_i) {
+                                                            CgVpqArgs vp, float* __restrict__ out_d,
+                                                            long long* __restrict__ out_i) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cg_s[];
   __shared__ int np_s;
-  const CgLayout L = cg_layout(n, itopk, width, gd, S, max_iter);
+  __shared__ float qn_s;
+  const CgLayout L = VPQ ? cg_layout(n, itopk, width, gd, S, max_iter, vp.M, vp.ksub, vp.nv)
+                         : cg_layout(n, itopk, width, gd, S, max_iter);
   float* qs = reinterpret_cast<float*>(cg_s + L.q);
   u64* buf = reinterpret_cast<u64*>(cg_s + L.buf);
   int* cand = reinterpret_cast<int*>(cg_s + L.cand);
@@ -306,6 +430,36 @@ __global__ __launch_bounds__(CG_T) void cagra_search_kernel(const float* __restr
   for (int i = t; i < (1 << L.lg_slots); i += CG_T) vis[i] = -1;
   for (int i = t; i < itopk; i += CG_T) buf[i] = CG_EMPTY;
   __syncthreads();
+  CgScore sc = {};
+  sc.qs = qs;
+  if constexpr (VPQ) {  // the query's tables: T, B and ||q||^2, independent of the list
+    float* T = reinterpret_cast<float*>(cg_s + L.tab);
+    float* B = reinterpret_cast<float*>(cg_s + L.bias);
+    srml_pq::pq_build_lut(qs, vp.cbT, vp.M, vp.ksub, n / vp.M, 1, T);
+    cg_center_dots(qs, vp.centers, vp.nv, n, vp.bvec, B);
+    if (wid == 0) {
+      float a = 0.f;
+      for (int d = lane; d < n; d += 64) a = fmaf(qs[d], qs[d], a);
+      a = wave_sum(a);
+      if (lane == 0) qn_s = a;
+    }
+    __syncthreads();
+    sc.codes = vp.codes;
+    sc.labels = vp.labels;
+    sc.xn = vp.xn;
+    sc.T = T;
+    sc.B = B;
+    sc.qn = qn_s;
+    sc.M = vp.M;
+    sc.ksub = vp.ksub;
+    sc.nv = vp.nv;
+    sc.cvec = vp.cvec;
+  } else {
+    sc.X = X;
+    sc.ldx = ldx;
+    sc.n = n;
+    sc.vec = vec;
+  }
   for (int i = t; i < L.c_init; i += CG_T) {  // the seeds, duplicates dropped through the table
     int id = -1;
     if (i < S) {
@@ -315,7 +469,7 @@ __global__ __launch_bounds__(CG_T) void cagra_search_kernel(const float* __restr
     cand[i] = id;
   }
   __syncthreads();
-  cg_round(qs, X, ldx, n, vec, cand, L.c_init, buf, L.p_init, itopk);
+  cg_round<VPQ>(sc, cand, L.c_init, buf, L.p_init, itopk);
   for (int it = 0; it < max_iter; ++it) {  // everything that steers this loop is block-uniform
     if (wid == 0) {  // the first `width` unexpanded entries, in list order
       int found = 0;
@@ -350,7 +504,7 @@ __global__ __launch_bounds__(CG_T) void cagra_search_kernel(const float* __restr
       cand[i] = id;
     }
     __syncthreads();
-    cg_round(qs, X, ldx, n, vec, cand, L.c_iter, buf, L.p_iter, itopk);
+    cg_round<VPQ>(sc, cand, L.c_iter, buf, L.p_iter, itopk);
   }
   for (int j = t; j < k; j += CG_T) {
     const u64 key = buf[j];
@@ -406,10 +560,57 @@ SRML_API int srml_cagra_search_f32(const float* Q, long nq, int n, long ldq, con
   const CgLayout L = cg_layout(n, itopk, width, gd, S, max_iter);
   if (L.total + CG_STATIC_LDS > CG_LDS_TOTAL) return -9;
   if (L.total > 32 * 1024)
-    (void)hipFuncSetAttribute((const void*)cagra_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)cagra_search_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)L.total);
   const int vec = (ldx % 4 == 0) && (((uintptr_t)X & 15) == 0);
-  hipLaunchKernelGGL(cagra_search_kernel, dim3((unsigned)nq), dim3(CG_T), L.total, stream, Q, n, ldq, X, N, ldx, F, gd,
-                     seeds, S, k, itopk, width, max_iter, min_iter, vec, out_d, out_i);
+  hipLaunchKernelGGL(cagra_search_kernel<false>, dim3((unsigned)nq), dim3(CG_T), L.total, stream, Q, n, ldq, X, N, ldx,
+                     F, gd, seeds, S, k, itopk, width, max_iter, min_iter, vec, CgVpqArgs{}, out_d, out_i);
+  return srml_status();
+}
+
+inline bool cg_vpq_shape_ok(int n, int M, int ksub, int nv) {
+  return M >= 1 && M <= CG_MMAX && n % M == 0 && ksub >= 1 && ksub <= CG_KSUBMAX && nv >= 1 && nv <= CG_VQ_MAX;
+}
+
+// LDS bytes of one VPQ search workgroup: srml_cagra_lds_bytes plus the T and B segments.
+SRML_API long srml_cagra_vpq_lds_bytes(int n, int itopk, int width, int gd, int S, int max_iter, int M, int ksub,
+                                       int nv) {
+  if (n < 1 || itopk < 1 || width < 1 || gd < 1 || S < 1 || max_iter < 0 || max_iter > 65536 || M < 1 || ksub < 1 ||
+      nv < 1 || (long)M * ksub > (long)CG_MMAX * CG_KSUBMAX || nv > CG_VQ_MAX)
+    return -1;
+  return (long)(cg_layout(n, itopk, width, gd, S, max_iter, M, ksub, nv).total + CG_STATIC_LDS);
+}
+
+// The search of srml_cagra_search_f32 over VPQ-compressed items: vector-quantiser centres
+// [nv, n] and labels [N], transposed codebooks cbT [M, n / M, ksub], codes u8 [N, M] row-major and
+// xn[i] = ||x^_i||^2. out_d holds the keys (see the file header), ascending with the positions.
+SRML_API int srml_cagra_search_vpq_f32(const float* Q, long nq, int n, long ldq, const float* centers, int nv,
+                                       const int* labels, const float* cbT, const unsigned char* codes,
+                                       const float* xn, int M, int ksub, long N, const int* F, int gd,
+                                       const int* seeds, int S, int k, int itopk, int width, int max_iter,
+                                       int min_iter, float* out_d, long long* out_i, hipStream_t stream) {
+  if (nq <= 0) return 0;
+  if (!cg_search_shape_ok(n, N, gd, S, k, itopk, width, max_iter, min_iter) || !cg_vpq_shape_ok(n, M, ksub, nv) ||
+      ldq < n || nq > srml_max_blocks(CG_T))
+    return -8;
+  const CgLayout L = cg_layout(n, itopk, width, gd, S, max_iter, M, ksub, nv);
+  if (L.total + CG_STATIC_LDS > CG_LDS_TOTAL) return -9;
+  if (L.total > 32 * 1024)
+    (void)hipFuncSetAttribute((const void*)cagra_search_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)L.total);
+  CgVpqArgs vp;
+  vp.centers = centers;
+  vp.labels = labels;
+  vp.cbT = cbT;
+  vp.codes = codes;
+  vp.xn = xn;
+  vp.nv = nv;
+  vp.M = M;
+  vp.ksub = ksub;
+  vp.cvec = (M % 4 == 0) && (((uintptr_t)codes & 3) == 0);
+  vp.bvec = (n % 4 == 0) && (((uintptr_t)centers & 15) == 0);
+  hipLaunchKernelGGL(cagra_search_kernel<true>, dim3((unsigned)nq), dim3(CG_T), L.total, stream, Q, n, ldq,
+                     (const float*)nullptr, N, 0L, F, gd, seeds, S, k, itopk, width, max_iter, min_iter, 0, vp, out_d,
+                     out_i);
   return srml_status();
 }

@@ -31,7 +31,7 @@ _LONG_RESULT = ("srml_rf_bootstrap_ws", "srml_logreg_fold_ws", "srml_qn_mb_scrat
                 "srml_rf_partition_ws", "srml_dbscan_labels_ws", "srml_umap_categorical_ws",
                 "srml_umap_epoch_sync_ws",
                 "srml_label_sort_ws", "srml_radix_sort_ws", "srml_lloyd_moved_ws", "srml_sum_f32_ws", "srml_sum_sq_ws",
-                "srml_cagra_lds_bytes")
+                "srml_cagra_lds_bytes", "srml_cagra_vpq_lds_bytes")
 SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_col_moments_f32": (_P, _L, _I, _L, _P, _P, _P),
     "srml_col_moments_f64": (_P, _L, _I, _L, _P, _P, _P),
@@ -276,6 +276,9 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_cagra_merge_i32": (_P, _L, _I, _P, _P, _L, _P, _P),
     "srml_cagra_lds_bytes": (_I, _I, _I, _I, _I, _I),
     "srml_cagra_search_f32": (_P, _L, _I, _L, _P, _L, _L, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P),
+    "srml_cagra_vpq_lds_bytes": (_I, _I, _I, _I, _I, _I, _I, _I, _I),
+    "srml_cagra_search_vpq_f32": (_P, _L, _I, _L, _P, _I, _P, _P, _P, _P, _I, _I, _L, _P, _I, _P, _I, _I, _I, _I, _I,
+                                  _I, _P, _P, _P),
 }
 
 _lock = threading.Lock()

@@ -7,10 +7,14 @@ warm-up, with the configurations alternating inside every repetition. Recall is 
 search on the first ``--recall-queries`` queries. The graph build is split into its phases (kNN
 graph, prune, merge). ``cagra_itopk64_seeds1024`` is itopk_size 64 with num_random_samplings 16
 (``cagra_itopk128_seeds1024``: 128 with 8): the blobs are separate components of the kNN graph, so
-a query is answered only when one of its seeds falls into its blob. Progress goes to stderr, the
-one JSON line to stdout and ``--out``.
+a query is answered only when one of its seeds falls into its blob. ``--compression
+pq_dim[,pq_bits[,vq_n_centers]]`` (repeatable) adds the VPQ codes to the same graph and runs every
+``cagra_*`` configuration on them as ``*_vpq<pq_dim>`` (refine_ratio 2), timed in the same alternation
+and with its recall beside the uncompressed one. Progress goes to stderr, the one JSON line to stdout
+and ``--out``.
 
     python tools/cagra_bench.py --out profiles/cagra_vs_ivf.json
+    python tools/cagra_bench.py --igd 63 --gd 32 --compression 32 --compression 64 --out profiles/cagra_vpq.json
 """
 import argparse
 import json
@@ -59,6 +63,7 @@ def main() -> None:
     ap.add_argument("--gd", type=int, default=64, help="graph_degree")
     ap.add_argument("--build-algo", default="auto")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--compression", action="append", default=[], metavar="pq_dim[,pq_bits[,vq_n_centers]]")
     ap.add_argument("--out", default="")
     ap.add_argument("--rehearse", action="store_true", help="run the CPU paths at a tiny size: its times mean nothing")
     a = ap.parse_args()
@@ -102,13 +107,22 @@ def main() -> None:
     res["graph_edges_per_row"] = float((cg.graph >= 0).sum().item()) / a.rows
     dump()
 
-    def cagra(itopk, nrs=1):
-        return lambda q: mk.cagra_knn(cg, q, a.k, (itopk, 1, 0, 0, nrs, 1), ctx)
+    def cagra(itopk, nrs=1, index=cg):
+        return lambda q: mk.cagra_knn(index, q, a.k, (itopk, 1, 0, 0, nrs, 1), ctx)
 
+    walks = {"cagra_itopk32": (32, 1), "cagra_itopk64": (64, 1), "cagra_itopk128": (128, 1),
+             "cagra_itopk64_seeds1024": (64, 16), "cagra_itopk128_seeds1024": (128, 8)}
     configs = {"ivfflat": lambda q: mk.ivf_knn(flat, q, a.k, a.nprobe, ctx),
-               "ivfpq_refine4": lambda q: mk.ivfpq_knn(pq, q, a.k, a.nprobe, 4, ctx),
-               "cagra_itopk32": cagra(32), "cagra_itopk64": cagra(64), "cagra_itopk128": cagra(128),
-               "cagra_itopk64_seeds1024": cagra(64, 16), "cagra_itopk128_seeds1024": cagra(128, 8)}
+               "ivfpq_refine4": lambda q: mk.ivfpq_knn(pq, q, a.k, a.nprobe, 4, ctx)}
+    configs.update({name: cagra(*w) for name, w in walks.items()})
+    res["compress_s"] = {}
+    for spec in a.compression:  # the same graph and rows with the VPQ arrays beside them
+        v = [int(x) for x in spec.split(",")]
+        comp = (v[1] if len(v) > 1 else 8, v[0], v[2] if len(v) > 2 else 0, 25)
+        cgc = mk.CagraIndex(cg.items, cg.ids, cg.graph)
+        res["compress_s"][spec] = timed(lambda: mk.compress_cagra(cgc, comp, 1), dev)[0]
+        say("compression %s %.2f s, %d centres" % (spec, res["compress_s"][spec], cgc.vq_centers.shape[0]))
+        configs.update({"%s_vpq%d" % (name, v[0]): cagra(*w, index=cgc) for name, w in walks.items()})
     Qr = Q[: a.recall_queries]
     _, exact = mk.exact_knn(X, ids, Qr, a.k, ctx)
     res["recall_at_k"] = {}
