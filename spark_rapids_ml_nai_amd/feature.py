@@ -17,6 +17,7 @@ from .core.base import FitInput, _Estimator, _Model
 from .core.dataframe import DataFrame
 from .core.linalg import DenseMatrix, DenseVector
 from .core.params import (
+    HasEnableSparseDataOptim,
     HasInputCol,
     HasInputCols,
     HasOutputCol,
@@ -39,8 +40,14 @@ class PCAClass(_BackendClass):
         return {"n_components": None, "svd_solver": "auto", "verbose": False, "whiten": False}
 
 
-class _PCAParams(_BackendParams, HasInputCol, HasInputCols, HasOutputCol):
+class _PCAParams(_BackendParams, HasInputCol, HasInputCols, HasOutputCol, HasEnableSparseDataOptim):
     k = Param(Params._dummy(), "k", "the number of principal components (> 0)", typeConverter=TypeConverters.toInt)
+
+    def __init__(self) -> None:
+        super().__init__()
+        # None (first row decides) would re-route existing fits of sparse vector columns to the CSR
+        # Gram kernel and change their last bits: sparse input is opt-in, as for KMeans
+        self._setDefault(enable_sparse_data_optim=False)
 
     def getK(self) -> int:
         return self.getOrDefault(self.k)
@@ -69,11 +76,14 @@ class PCA(PCAClass, _Estimator, _PCAParams):
 
     @keyword_only
     def __init__(self, *, k: Optional[int] = None, inputCol: Optional[Union[str, List[str]]] = None,
-                 outputCol: Optional[str] = None, num_workers: Optional[int] = None,
-                 verbose: Union[int, bool] = False, **kwargs: Any) -> None:
+                 outputCol: Optional[str] = None, enable_sparse_data_optim: Optional[bool] = False,
+                 num_workers: Optional[int] = None, verbose: Union[int, bool] = False, **kwargs: Any) -> None:
         super().__init__()
         self._setDefault(outputCol=self.uid + "__output")
         self._set_params(**self._input_kwargs)
+
+    def _supports_sparse(self) -> bool:
+        return True
 
     def setK(self, value: int) -> "PCA":
         return self._set_params(k=value)
@@ -132,6 +142,10 @@ class PCAModel(PCAClass, _Model, _PCAParams):
 
         return to_spark_pca_model(self)
 
+    def _transform_supports_sparse(self) -> bool:
+        # sparse-vector partitions stay CSR unless the Param says densify (False, the default)
+        return self.getOrDefault("enable_sparse_data_optim") is not False
+
     def _get_transform_func(self, dataset: DataFrame) -> Tuple[Callable, Callable]:
         comps = np.asarray(self.components_, dtype=np.float64)
         out_col = self.getOrDefault("outputCol")
@@ -141,10 +155,14 @@ class PCAModel(PCAClass, _Model, _PCAParams):
             return torch.from_numpy(comps.astype(np_dt)).to(ctx.device)
 
         def predict(C: torch.Tensor, X: Any, ctx: WorkerContext) -> Dict[str, np.ndarray]:
-            from .core.base import to_device
+            from .core.base import CSR, to_device
             from .models.pca import pca_transform
 
             Xd = to_device(X, ctx.device, C.dtype)
+            if isinstance(Xd, CSR):  # a sparse-vector partition: the uncentred rows, nothing densified
+                from . import ops
+
+                return {out_col: ops.csr_spmm(Xd, C.T.contiguous()).cpu().numpy().astype(np_dt)}
             return {out_col: pca_transform(Xd, C).cpu().numpy().astype(np_dt)}
 
         return construct, predict

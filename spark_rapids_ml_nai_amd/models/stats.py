@@ -7,6 +7,9 @@ non-streaming path), then corrected exactly in fp64:
 
     C_r = sum (x - mu0)(x - mu0)^T - m_r d d^T,          d = mean_r - mu0   (local scatter)
     C   = sum_r [ C_r + m_r (mean_r - mu)(mean_r - mu)^T ]                 (global, one all-reduce)
+
+A ``CSR`` shard (sparse vector column, ``enable_sparse_data_optim``) cannot be centred first: its raw
+Gram (mu0 = 0) is formed with every product and sum in fp64 (``ops.csr_gram``) and corrected the same way.
 """
 from __future__ import annotations
 
@@ -32,9 +35,12 @@ class ScatterStats:
 
 def scatter_stats(X: torch.Tensor, ctx: WorkerContext, m_total: int, stream: Any = None,
                   y: Optional[torch.Tensor] = None, need_sq: bool = True) -> ScatterStats:
+    from ..core.base import CSR
+
+    sparse = isinstance(X, CSR)  # a sparse vector column kept CSR: no streaming, ``stream`` is unused
     n = X.shape[1]
     dev = X.device
-    chunks = stream.chunks() if stream is not None else [(0, X.shape[0], X)]
+    chunks = [] if sparse else stream.chunks() if stream is not None else [(0, X.shape[0], X)]
     # the two all-reduce buffers are allocated whole and the accumulators are views of them: small =
     # [column sums | sums of squares | y sum, y sum of squares], big = [scatter | X^T y]
     ns = n + (n if need_sq else 0)
@@ -55,6 +61,17 @@ def scatter_stats(X: torch.Tensor, ctx: WorkerContext, m_total: int, stream: Any
         if y is not None:
             ops.xtv(Xc, y[r0:r1].view(-1, 1), out=xty)
         m_r += r1 - r0
+    if sparse:
+        # rows that cannot be centred first: the raw Gram (shift mu0 = 0) with every product and sum in
+        # fp64 (csrc/csr_gram.hip), re-centred below like the dense one
+        cs, cq = ops.csr_col_moments(X)
+        s.copy_(cs)
+        if need_sq:
+            q.copy_(cq)
+        ops.csr_gram(X, out=G)
+        if y is not None:
+            ops.csr_xty(X, y, out=xty.view(-1))
+        m_r = X.shape[0]
     ops.gram_mirror(G)
     if mu0 is None:
         mu0 = ops.zeros(n, dtype=torch.float64, device=dev)

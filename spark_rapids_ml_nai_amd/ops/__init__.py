@@ -4508,6 +4508,105 @@ def csr_gather_dense(A: Any, rows: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------
+# Gram matrix and X^T y of CSR rows (csrc/csr_gram.hip): LinearRegression / PCA on sparse features
+_CSR_GRAM_WIN_BYTES = 1 << 30  # window-table budget of one launch (int32, (n / T + 1) entries per row)
+
+
+def csr_gram_config() -> Tuple[int, int, int]:
+    """(tile width T, rows a wave takes at once = the slab unit R, segment chunk C) of
+    ``srml_csr_gram_*``, read from the library."""
+    cfg = native.lib().srml_csr_gram_config
+    return int(cfg(0)), int(cfg(1)), int(cfg(2))
+
+
+def _csr_block(A: Any, a: int, b: int, r0: int, r1: int) -> torch.Tensor:
+    """Rows r0 .. r1 of the CSR ``A`` (absolute offsets) as a torch CSR tensor in fp64."""
+    ip = A.indptr[r0: r1 + 1]
+    p0, p1 = int(ip[0]), int(ip[-1])
+    return torch.sparse_csr_tensor(ip - p0, A.indices[p0:p1].long(), A.data[p0:p1].double(), (r1 - r0, int(A.shape[1])))
+
+
+def csr_gram(A: Any, out: Optional[torch.Tensor] = None, tile: int = 0) -> torch.Tensor:
+    """out (fp64 n x n, UPPER triangle only) += A^T A for the CSR rows ``A`` (indptr int64, indices
+    int32, values fp32 or fp64; ``indptr`` may be a slice of a larger matrix's row offsets); returns
+    out. Complete it with ``gram_mirror``. Column indices must be ASCENDING within each row and in
+    [0, n): the kernel's window table is a bisection of each row, as in ``srml_csr_pairdist_f32``;
+    checked once per matrix, ``ValueError`` before any launch otherwise.
+
+    Every product is formed in fp64 (exact for fp32 values) and added in fp64, so with u = 2^-53 and
+    P = |A|^T |A| the error of a cell is at most (m + 2) u P; a cell that no row touches with both
+    columns stays exactly 0.0. Device: ``srml_csr_gram_{f32,f64}`` (``tile``: 64, 128 or 0 for the
+    kernel's default), rows chunked so that the window table stays under ``_CSR_GRAM_WIN_BYTES``.
+    Deterministic mode: each product is rounded to the grid 2^-s, 2^s =
+    ``csr_fixed_scale(m, max|value|^2)``, and added as an i64 integer in LDS and in an n x n i64
+    buffer, converted once: bit-identical on every call, at most 2^-(s+1) more error per product.
+    CPU tensors: torch sparse products of row chunks in fp64 (a fixed order in either mode)."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    if out is None:
+        out = zeros((n, n), dtype=torch.float64, device=dev)
+    elif out.shape != (n, n) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+        raise ValueError("csr_gram: out must be a contiguous fp64 (%d, %d) tensor on %s" % (n, n, dev))
+    if m == 0 or n == 0 or b == a:
+        return out
+    if not A.data.is_cuda:
+        step = max(1, _CSR_KM_TORCH_ELEMS // n)
+        for r0 in range(0, m, step):
+            S = _csr_block(A, a, b, r0, min(m, r0 + step))
+            out += torch.triu(S.t() @ S.to_dense())
+        return out
+    T = int(tile) or csr_gram_config()[0]
+    W = (n + T - 1) // T
+    scale, acc = 0.0, out
+    if deterministic():
+        vmax = float(A.data[a:b].abs().max().item())
+        scale = csr_fixed_scale(m, vmax * vmax)
+        acc = zeros((n, n), dtype=torch.int64, device=dev)
+    step = max(1, min(m, int(_CSR_GRAM_WIN_BYTES) // (4 * (W + 1))))
+    win = torch.empty(step * (W + 1), dtype=torch.int32, device=dev)
+    indptr, st = _c(A.indptr), native.stream(dev)
+    for r0 in range(0, m, step):
+        r = min(step, m - r0)
+        rc = native.call_status("srml_csr_gram_" + _sfx(A), indptr[r0:].data_ptr(), A.indices.data_ptr(),
+                                A.data.data_ptr(), r, n, T, win.data_ptr(), scale, acc.data_ptr(), st)
+        if rc < 0:
+            raise ValueError("srml_csr_gram refused the launch (status %d: -1 grid overflow, -2 tile width) for %d "
+                             "rows, n=%d, tile=%d" % (rc, r, n, T))
+        if rc != 0:
+            raise RuntimeError("srml_csr_gram launch failed with HIP status %d" % rc)
+    if scale:
+        native.call("srml_csr_gram_finish", acc.data_ptr(), n, 1.0 / scale, out.data_ptr(), st)
+    return out
+
+
+def csr_xty(A: Any, y: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (fp64 n) += A^T y for the CSR rows ``A`` (as in ``csr_gram``) and ``y`` (m values, read in
+    fp32 or fp64 as they come; other dtypes are converted to fp64); returns out. Device:
+    ``srml_csr_xty_{f32,f64}``, one wave per row, one fp64 atomic per non-zero (in either mode: the
+    order of the additions is not fixed). CPU tensors: a torch sparse product in fp64."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    if y.numel() != m:
+        raise ValueError("csr_xty: %d values of y for %d rows" % (y.numel(), m))
+    if out is None:
+        out = zeros(n, dtype=torch.float64, device=dev)
+    elif out.numel() != n or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+        raise ValueError("csr_xty: out must be a contiguous fp64 tensor of %d values on %s" % (n, dev))
+    if m == 0 or b == a:
+        return out
+    y = y.to(dev).view(-1)
+    if not A.data.is_cuda:
+        out.view(-1).add_((_csr_block(A, a, b, 0, m).t() @ y.double().view(-1, 1)).view(-1))
+        return out
+    yc = _c(y if y.dtype in (torch.float32, torch.float64) else y.double())
+    native.call("srml_csr_xty_" + _sfx(A), _c(A.indptr).data_ptr(), A.indices.data_ptr(), A.data.data_ptr(), m,
+                yc.data_ptr(), int(yc.dtype == torch.float64), out.data_ptr(), native.stream(dev))
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # Logistic loss + gradient accumulation for the on-device quasi-Newton driver (models/qn.py)
 def _is_csr(X) -> bool:
     return hasattr(X, "indptr") and hasattr(X, "indices")

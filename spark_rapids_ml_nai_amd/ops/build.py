@@ -46,7 +46,7 @@ def _headers() -> List[str]:
 
 # Translation units built without the packed fp32 VALU instructions (v_pk_add / mul / fma_f32): their
 # inner loops are per-lane scalar chains, and the keys they sort must be the scalar results.
-NO_PACKED_FP32 = ("nnd.hip", "cagra.hip")
+NO_PACKED_FP32 = ("nnd.hip", "cagra.hip", "csr_gram.hip")
 
 
 def _flags(src: str = "") -> List[str]:

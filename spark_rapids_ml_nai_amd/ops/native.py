@@ -237,6 +237,14 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_csr_cluster_sums_f32": (_P, _P, _P, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_csr_cluster_sums_f64": (_P, _P, _P, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_csr_cluster_sums_finish": (_P, _L, _D, _P),
+    # Gram of CSR rows: (row offsets, indices, values, rows), n, tile width (0: default), window table, fixed-point
+    # scale (0: fp64 atomics), out / i64 buffer, n, 1 / scale, out / (.. rows), y, y is fp64, out
+    "srml_csr_gram_config": (_I,),
+    "srml_csr_gram_f32": (_P, _P, _P, _L, _I, _I, _P, _D, _P, _P),
+    "srml_csr_gram_f64": (_P, _P, _P, _L, _I, _I, _P, _D, _P, _P),
+    "srml_csr_gram_finish": (_P, _I, _D, _P, _P),
+    "srml_csr_xty_f32": (_P, _P, _P, _L, _P, _I, _P, _P),
+    "srml_csr_xty_f64": (_P, _P, _P, _L, _P, _I, _P, _P),
     "srml_confusion_counts": (_P, _I, _P, _I, _L, _I, _P, _P),
     "srml_logloss_sum": (_P, _I, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_reg_moments": (_P, _I, _P, _I, _L, _P, _P),

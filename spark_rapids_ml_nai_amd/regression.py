@@ -19,6 +19,7 @@ from .core.linalg import DenseVector, as_dense_array
 from .core.params import (
     HasAggregationDepth,
     HasElasticNetParam,
+    HasEnableSparseDataOptim,
     HasFeaturesCol,
     HasFeaturesCols,
     HasFitIntercept,
@@ -84,7 +85,7 @@ class LinearRegressionClass(_BackendClass):
 class _LinearRegressionParams(_BackendParams, HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredictionCol,
                               HasMaxIter, HasRegParam, HasElasticNetParam, HasTol, HasFitIntercept,
                               HasStandardization, HasWeightCol, HasSolver, HasAggregationDepth, HasLoss,
-                              HasMaxBlockSizeInMB, _FeaturesColMixin):
+                              HasMaxBlockSizeInMB, HasEnableSparseDataOptim, _FeaturesColMixin):
     epsilon = Param(Params._dummy(), "epsilon", "The shape parameter to control the amount of robustness (huber).",
                     typeConverter=TypeConverters.toFloat)
 
@@ -94,6 +95,9 @@ class _LinearRegressionParams(_BackendParams, HasFeaturesCol, HasFeaturesCols, H
                          solver="auto", loss="squaredError", epsilon=1.35, elasticNetParam=0.0,
                          aggregationDepth=2, maxBlockSizeInMB=0.0, featuresCol="features", labelCol="label",
                          predictionCol="prediction")
+        # None (first row decides) would re-route existing fits of sparse vector columns to the CSR
+        # Gram kernel and change their last bits: sparse input is opt-in, as for KMeans
+        self._setDefault(enable_sparse_data_optim=False)
 
     def getEpsilon(self) -> float:
         return self.getOrDefault("epsilon")
@@ -111,9 +115,13 @@ class LinearRegression(LinearRegressionClass, _EstimatorSupervised, _LinearRegre
                  predictionCol: str = "prediction", maxIter: int = 100, regParam: float = 0.0,
                  elasticNetParam: float = 0.0, tol: float = 1e-6, fitIntercept: bool = True,
                  standardization: bool = True, solver: str = "auto", loss: str = "squaredError",
+                 enable_sparse_data_optim: Optional[bool] = False,
                  num_workers: Optional[int] = None, verbose: Union[int, bool] = False, **kwargs: Any) -> None:
         super().__init__()
         self._set_params(**self._input_kwargs)
+
+    def _supports_sparse(self) -> bool:
+        return True
 
     def setMaxIter(self, value: int) -> "LinearRegression":
         return self._set_params(maxIter=value)
@@ -248,6 +256,10 @@ class LinearRegressionModel(LinearRegressionClass, _ModelWithPredictionCol, _Lin
 
         return to_spark_linear_regression_model(self)
 
+    def _transform_supports_sparse(self) -> bool:
+        # sparse-vector partitions stay CSR unless the Param says densify (False, the default)
+        return self.getOrDefault("enable_sparse_data_optim") is not False
+
     def _get_transform_func(self, dataset: DataFrame) -> Tuple[Callable, Callable]:
         coef = np.asarray(self.coef_, dtype=np.float64)
         intercept = float(self.intercept_)
@@ -258,10 +270,14 @@ class LinearRegressionModel(LinearRegressionClass, _ModelWithPredictionCol, _Lin
             return torch.from_numpy(coef.astype(np_dt)).to(ctx.device)
 
         def predict(w: torch.Tensor, X: Any, ctx: WorkerContext) -> Dict[str, np.ndarray]:
-            from .core.base import to_device
+            from .core.base import CSR, to_device
             from .models.linear import linear_predict
 
             Xd = to_device(X, ctx.device, w.dtype)
+            if isinstance(Xd, CSR):  # a sparse-vector partition: one pass over the non-zeros
+                from . import ops
+
+                return {pred_col: ctx.output(ops.csr_spmm(Xd, w.view(-1, 1)).view(-1).double() + intercept)}
             return {pred_col: ctx.output(linear_predict(Xd, w, intercept).double())}
 
         return construct, predict

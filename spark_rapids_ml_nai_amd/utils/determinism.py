@@ -11,7 +11,9 @@ switches the affected kernels to fixed-order variants:
   sums independent of the row order;
 * Gram / covariance (PCA, LinearRegression normal equations) -> each row chunk stores its
   partial tiles into a workspace (<= 64 chunks, <= 1 GB) folded in chunk order, instead of
-  fp64 atomics (same fp32-per-chunk / fp64-across-chunk precision);
+  fp64 atomics (same fp32-per-chunk / fp64-across-chunk precision); on CSR rows (``ops.csr_gram``)
+  every product is rounded to an i64 fixed-point grid and added with integer atomics in LDS and in
+  memory, converted to fp64 once (the sparse column moments and X^T y keep their fp64 atomics);
 * fp64 GEMMs (``ops.dgemm``: X^T V, Krylov products) always fold split-K partials in index
   order, deterministic in either mode;
 * LogisticRegression -> the two-pass path (residual stage + MFMA X^T R) with ordered block-partial
