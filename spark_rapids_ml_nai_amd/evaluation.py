@@ -1,20 +1,21 @@
 """``pyspark.ml.evaluation``-compatible evaluators for the Spark-free data plane.
 
 ``RegressionEvaluator`` (rmse, mse, r2, mae, var), ``MulticlassClassificationEvaluator``
-(the 14 Spark metrics) and ``BinaryClassificationEvaluator`` (areaUnderROC / areaUnderPR)
-evaluate a transformed DataFrame; the CrossValidator fast path skips the transformed frame
-and merges per-partition statistics computed on the device (``metrics/``).
+(the 14 Spark metrics), ``BinaryClassificationEvaluator`` (areaUnderROC / areaUnderPR) and
+``ClusteringEvaluator`` (silhouette, squaredEuclidean / cosine) evaluate a transformed DataFrame;
+the CrossValidator fast path skips the transformed frame and merges per-partition statistics
+computed on the device (``metrics/``).
 When pyspark is installed its evaluators are accepted as well (same getters).
 """
 from __future__ import annotations
 
-from typing import Any, Optional
+from typing import Any, List, Optional, Union
 
 import numpy as np
 
 from .core.dataframe import DataFrame, as_dataframe
-from .core.params import HasLabelCol, HasPredictionCol, HasProbabilityCol, HasRawPredictionCol, Param, Params, \
-    TypeConverters, keyword_only
+from .core.params import HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredictionCol, HasProbabilityCol, \
+    HasRawPredictionCol, Param, Params, TypeConverters, keyword_only
 from .metrics import ClassificationSummary, MulticlassMetrics, RegressionMetrics, RegressionSummary, binary_aupr, \
     binary_auc
 
@@ -145,3 +146,73 @@ class BinaryClassificationEvaluator(Evaluator, HasLabelCol, HasRawPredictionCol)
         if self.getMetricName() == "areaUnderPR":
             return binary_aupr(y, score)
         return binary_auc(y, score)
+
+
+class ClusteringEvaluator(Evaluator, HasPredictionCol, HasFeaturesCol, HasFeaturesCols):
+    """Silhouette of a clustering (``pyspark.ml.evaluation.ClusteringEvaluator``): Spark's closed
+    form, every row scored against the k cluster summaries on the fused MFMA kernel."""
+    metricName = Param(Params._dummy(), "metricName", "metric name in evaluation (silhouette)",
+                       typeConverter=TypeConverters.toString)
+    distanceMeasure = Param(Params._dummy(), "distanceMeasure", "The distance measure. Supported options: "
+                            "'squaredEuclidean' and 'cosine'.", typeConverter=TypeConverters.toString)
+    weightCol = Param(Params._dummy(), "weightCol", "weight column name.", typeConverter=TypeConverters.toString)
+
+    @keyword_only
+    def __init__(self, *, predictionCol: str = "prediction", featuresCol: Union[str, List[str]] = "features",
+                 metricName: str = "silhouette", distanceMeasure: str = "squaredEuclidean",
+                 weightCol: Optional[str] = None) -> None:
+        super().__init__()
+        self._setDefault(metricName="silhouette", distanceMeasure="squaredEuclidean", predictionCol="prediction",
+                         featuresCol="features")
+        kw = {k: v for k, v in self._input_kwargs.items() if v is not None}
+        fc = kw.pop("featuresCol", None)
+        self._set(**kw)
+        if fc is not None:
+            self.setFeaturesCol(fc)
+        self._check()
+
+    def _check(self) -> None:
+        from .ops import SILHOUETTE_MEASURES
+
+        if self.getMetricName() != "silhouette":
+            raise ValueError("ClusteringEvaluator: metricName must be 'silhouette', got %r" % self.getMetricName())
+        if self.getDistanceMeasure() not in SILHOUETTE_MEASURES:
+            raise ValueError("ClusteringEvaluator: distanceMeasure must be one of %s, got %r"
+                             % (SILHOUETTE_MEASURES, self.getDistanceMeasure()))
+
+    def getDistanceMeasure(self) -> str:
+        return self.getOrDefault("distanceMeasure")
+
+    def setDistanceMeasure(self, value: str) -> "ClusteringEvaluator":
+        return self._set(distanceMeasure=value)
+
+    def getWeightCol(self) -> Optional[str]:
+        return self.getOrDefault("weightCol") if self.isDefined("weightCol") else None
+
+    def setWeightCol(self, value: str) -> "ClusteringEvaluator":
+        return self._set(weightCol=value)
+
+    def setFeaturesCol(self, value: Union[str, List[str]]) -> "ClusteringEvaluator":
+        if isinstance(value, str):
+            self.clear(self.getParam("featuresCols"))
+            return self._set(featuresCol=value)
+        return self._set(featuresCols=list(value))
+
+    def _evaluate(self, dataset: Any) -> float:
+        from .core.base import _dense_from_df
+        from .models.silhouette import silhouette_score
+        from .parallel.context import local_device
+
+        self._check()
+        cols = self.getOrDefault("featuresCols") if self.isDefined("featuresCols") else None
+        col = None if cols else self.getOrDefault("featuresCol")
+        pc, wc = self.getOrDefault("predictionCol"), self.getWeightCol()
+        df = _local(dataset, (cols or [col]) + [pc] + ([wc] if wc else []))
+        parts = []
+        for t in df.partitions:
+            if t.num_rows == 0:
+                continue
+            p = DataFrame([t])
+            parts.append((_dense_from_df(p, col, cols, np.float32), p.to_numpy(pc, np.float64),
+                          p.to_numpy(wc, np.float64) if wc else None))
+        return silhouette_score(parts, self.getDistanceMeasure(), local_device())

@@ -16,7 +16,7 @@ from ..utils.determinism import deterministic
 
 __all__ = ["col_moments", "gram", "xw", "dgemm", "sign_flip", "is_native", "xtv", "row_sqnorm",
            "logreg_binary_loss_grad", "nearest_centroid", "cluster_sums", "csr_logreg_binary_loss_grad",
-           "csr_spmm", "csr_spmtm", "csr_col_moments", "logistic_loss_grad", "svc_path", "svc_loss_grad"]
+           "csr_spmm", "csr_spmtm", "csr_col_moments", "logistic_loss_grad", "svc_path", "svc_loss_grad", "silhouette"]
 
 
 def is_native(t: torch.Tensor) -> bool:
@@ -5127,3 +5127,188 @@ def reg_moments(y: torch.Tensor, pred: torch.Tensor) -> np.ndarray:
     native.call("srml_reg_moments", yk.data_ptr(), yi, pk.data_ptr(), pi, int(y.shape[0]), out.data_ptr(),
                 native.stream(y.device))
     return out.cpu().numpy().reshape(4, 3)
+
+
+# ------------------------------------------------------------------------------------------
+# Silhouette (csrc/silhouette.hip): Spark's closed form on the fused MFMA cluster-distance kernel
+SILHOUETTE_MEASURES = ("squaredEuclidean", "cosine")
+_SIL_CHUNK_ELEMS = 1 << 24  # rows x k of one fp64 chunk of the torch path
+
+
+def _sil_args(X: torch.Tensor, labels: torch.Tensor, weights: Optional[torch.Tensor], measure: str
+              ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    if measure not in SILHOUETTE_MEASURES:
+        raise ValueError("silhouette: distanceMeasure must be one of %s, got %r" % (SILHOUETTE_MEASURES, measure))
+    lab = labels.to(device=X.device)
+    if weights is None:
+        return lab, None
+    w = _c(weights.to(device=X.device, dtype=torch.float64))
+    if w.numel() and not bool((torch.isfinite(w) & (w >= 0)).all()):
+        raise ValueError("silhouette: weights must be finite and non-negative")
+    return lab, w
+
+
+def _sil_native(X: torch.Tensor) -> bool:
+    return X.is_cuda and X.dtype == torch.float32
+
+
+def _sil_scale(X: torch.Tensor, w: Optional[torch.Tensor]) -> torch.Tensor:
+    """fp32 1 / ||x_i|| of the device rows (cosine); a zero row that carries weight is an error."""
+    sq = row_sqnorm(X)
+    zero = sq == 0 if w is None else (sq == 0) & (w > 0)
+    if bool(zero.any()):
+        raise ValueError("silhouette: cosine distance is not defined for zero-length vectors")
+    return torch.where(sq > 0, sq.double().rsqrt(), torch.zeros_like(sq, dtype=torch.float64)).float()
+
+
+def silhouette_sums(X: torch.Tensor, labels: torch.Tensor, k: int, weights: Optional[torch.Tensor] = None,
+                    measure: str = "squaredEuclidean") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-cluster (N fp64 [k] = sum of w, Y fp64 [k, n] = sum of w x; cosine: of w x / ||x||) of one
+    block of rows; the summaries of several partitions add. Device: label-sorted segments summed in
+    fp64 in a fixed order (``srml_silhouette_sums_f32``)."""
+    lab, w = _sil_args(X, labels, weights, measure)
+    m, n = X.shape
+    if not _sil_native(X):
+        Xd = X.double()
+        wd = w if w is not None else torch.ones(m, dtype=torch.float64, device=X.device)
+        if measure == "cosine":
+            nrm = Xd.norm(dim=1)
+            if bool(((nrm == 0) & (wd > 0)).any()):
+                raise ValueError("silhouette: cosine distance is not defined for zero-length vectors")
+            Xd = Xd / torch.where(nrm > 0, nrm, torch.ones_like(nrm)).view(-1, 1)
+        N = torch.zeros(k, dtype=torch.float64, device=X.device).index_add_(0, lab.long(), wd)
+        Y = torch.zeros((k, n), dtype=torch.float64, device=X.device).index_add_(0, lab.long(), Xd * wd.view(-1, 1))
+        return N, Y
+    X = X if X.stride(1) == 1 else X.contiguous()
+    st = native.stream(X.device)
+    scale = _sil_scale(X, w) if measure == "cosine" else None
+    perm, off, _ = label_sort(lab, k)
+    N = torch.empty(k, dtype=torch.float64, device=X.device)
+    Y = torch.empty((k, n), dtype=torch.float64, device=X.device)
+    native.call("srml_silhouette_seg_scalars", perm.data_ptr(), off.data_ptr(), k, native.ptr(w), None, N.data_ptr(),
+                None, st)
+    cblocks = k * ((n + 255) // 256)
+    splits = int(max(1, min(64, m // max(1, k * 256), (4096 + cblocks - 1) // cblocks)))
+    ws = torch.empty(splits * k * n, dtype=torch.float64, device=X.device) if splits > 1 else None
+    native.call("srml_silhouette_sums_f32", X.data_ptr(), m, n, X.stride(0), perm.data_ptr(), off.data_ptr(), k,
+                native.ptr(scale), native.ptr(w), Y.data_ptr(), splits, native.ptr(ws), st)
+    return N, Y
+
+
+def silhouette_centre(N: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """The fp32 global weighted mean the squaredEuclidean path centres on (from merged summaries)."""
+    return (Y.sum(0) / N.sum()).float()
+
+
+def silhouette_psi(X: torch.Tensor, labels: torch.Tensor, k: int, mu: torch.Tensor,
+                   weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Psi' fp64 [k] = per-cluster sum of w ||x - mu||^2 of one block of rows (adds over partitions):
+    from the centred norms, never from an expanded sum of ||x||^2."""
+    lab, w = _sil_args(X, labels, weights, "squaredEuclidean")
+    if not _sil_native(X):
+        r = ((X.double() - mu.double().to(X.device)) ** 2).sum(1)
+        return torch.zeros(k, dtype=torch.float64, device=X.device).index_add_(0, lab.long(), r if w is None else r * w)
+    r = row_sqnorm(X, mu)
+    perm, off, _ = label_sort(lab, k)
+    psi = torch.empty(k, dtype=torch.float64, device=X.device)
+    native.call("srml_silhouette_seg_scalars", perm.data_ptr(), off.data_ptr(), k, native.ptr(w), r.data_ptr(), None,
+                psi.data_ptr(), native.stream(X.device))
+    return psi
+
+
+def _sil_formula(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    one = torch.ones_like(a)
+    return torch.where(a < b, 1 - a / torch.where(a < b, b, one),
+                       torch.where(a > b, b / torch.where(a > b, a, one) - 1, torch.zeros_like(a)))
+
+
+def silhouette(X: torch.Tensor, labels: torch.Tensor, k: int, weights: Optional[torch.Tensor] = None,
+               measure: str = "squaredEuclidean", stats: Optional[Tuple[torch.Tensor, ...]] = None,
+               rows_out: bool = False) -> Tuple[torch.Tensor, ...]:
+    """(sum of w_i s_i, sum of w_i[, s fp32 [m]]) of the rows' silhouette values under Spark's closed
+    form (``ClusteringEvaluator``): labels are dense ids in [0, k), ``stats`` = (N, Y, Psi') the
+    cluster summaries merged over every partition (``silhouette_sums`` / ``silhouette_psi``; Psi' is
+    unused for cosine), computed from ``X`` when absent. Device fp32 rows run the fused MFMA kernel
+    (``srml_silhouette_f32``): no m x k matrix, no centred copy of X, bit-identical run to run.
+    Other inputs run in fp64 on row chunks."""
+    lab, w = _sil_args(X, labels, weights, measure)
+    m, n = X.shape
+    cos = measure == "cosine"
+    if m == 0:
+        z = torch.zeros((), dtype=torch.float64, device=X.device)
+        return (z, z.clone(), torch.empty(0, dtype=torch.float32, device=X.device)) if rows_out else (z, z.clone())
+    if stats is None:
+        N, Y = silhouette_sums(X, lab, k, w, measure)
+        psi = None if cos else silhouette_psi(X, lab, k, silhouette_centre(N, Y), w)
+    else:
+        N, Y = stats[0].to(X.device), stats[1].to(X.device)
+        psi = None if cos else stats[2].to(X.device)
+    live = N > 0
+    if int(live.sum()) < 2:
+        raise ValueError("silhouette: Number of clusters must be greater than one")
+    Nd = torch.where(live, N, torch.ones_like(N))
+    sum_w = w.sum() if w is not None else torch.tensor(float(m), dtype=torch.float64, device=X.device)
+    if not _sil_native(X):
+        # the centre Psi' was taken about (D is invariant under the common translation)
+        mu = torch.zeros(n, dtype=torch.float64, device=X.device) if cos else silhouette_centre(N, Y).double()
+        Mc = Y / Nd.view(-1, 1) - mu
+        tc = torch.zeros_like(N) if cos else psi / Nd
+        s = torch.empty(m, dtype=torch.float64, device=X.device)
+        wd = w if w is not None else torch.ones(m, dtype=torch.float64, device=X.device)
+        step = max(1, _SIL_CHUNK_ELEMS // max(k, 1))
+        for r0 in range(0, m, step):
+            V = X[r0: r0 + step].double() - mu
+            lc, wc = lab[r0: r0 + step].long(), wd[r0: r0 + step]
+            if cos:
+                nrm = V.norm(dim=1)
+                if bool(((nrm == 0) & (wc > 0)).any()):
+                    raise ValueError("silhouette: cosine distance is not defined for zero-length vectors")
+                V = V / torch.where(nrm > 0, nrm, torch.ones_like(nrm)).view(-1, 1)
+                d = 1.0 - V @ Mc.T
+            else:
+                d = (V * V).sum(1).view(-1, 1) + tc.view(1, -1) - 2.0 * (V @ Mc.T)
+            d.clamp_min_(0)
+            d[:, ~live] = math.inf
+            own = d.gather(1, lc.view(-1, 1)).view(-1)
+            b = d.scatter(1, lc.view(-1, 1), math.inf).min(1).values
+            Nl = N[lc]
+            scored = (wc > 0) & (Nl > wc)
+            a = own * Nl / torch.where(scored, Nl - wc, torch.ones_like(Nl))
+            s[r0: r0 + step] = torch.where(scored, _sil_formula(a, b), torch.zeros_like(a))
+        out = ((wd * s).sum(), sum_w)
+        return out + (s.float(),) if rows_out else out
+    X = X if X.stride(1) == 1 else X.contiguous()
+    out, s = _sil_launch(X, k, _sil_operands(X, lab, w, cos, N, Y, psi), rows_out)
+    return (out[0], sum_w, s) if rows_out else (out[0], sum_w)
+
+
+def _sil_operands(X: torch.Tensor, lab: torch.Tensor, w: Optional[torch.Tensor], cos: bool, N: torch.Tensor,
+                  Y: torch.Tensor, psi: Optional[torch.Tensor]) -> Tuple[Any, ...]:
+    """The kernel's small operands from the merged summaries: (mu, scale, r, m_c fp32 [k, n], t_c, N,
+    labels int32, w, alpha); the centred means and t_c are formed in fp64 and rounded once."""
+    live = N > 0
+    Nd = torch.where(live, N, torch.ones_like(N))
+    if cos:
+        mu32, scale, rvec, tc32, alpha = None, _sil_scale(X, w), None, None, 1.0
+        Mc = Y / Nd.view(-1, 1)
+    else:
+        mu32 = _c(silhouette_centre(N, Y))
+        scale, rvec, alpha = None, row_sqnorm(X, mu32), 2.0
+        Mc = Y / Nd.view(-1, 1) - mu32.double()
+        tc32 = _c((psi / Nd).float())
+    M32 = (Mc * live.view(-1, 1)).float().contiguous()
+    return mu32, scale, rvec, M32, tc32, _c(N.double()), _c(lab.to(torch.int32)), w, alpha
+
+
+def _sil_launch(X: torch.Tensor, k: int, operands: Tuple[Any, ...], rows_out: bool
+                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    mu32, scale, rvec, M32, tc32, Nc, lab32, w, alpha = operands
+    m, n = X.shape
+    dev = X.device
+    s = torch.empty(m, dtype=torch.float32, device=dev) if rows_out else None
+    part = torch.empty((m + 127) // 128, dtype=torch.float64, device=dev)
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    native.call("srml_silhouette_f32", X.data_ptr(), m, n, X.stride(0), native.ptr(mu32), native.ptr(scale),
+                native.ptr(rvec), M32.data_ptr(), k, M32.stride(0), native.ptr(tc32), Nc.data_ptr(), lab32.data_ptr(),
+                native.ptr(w), float(alpha), native.ptr(s), part.data_ptr(), out.data_ptr(), native.stream(dev))
+    return out, s

@@ -245,6 +245,11 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_csr_gram_finish": (_P, _I, _D, _P, _P),
     "srml_csr_xty_f32": (_P, _P, _P, _L, _P, _I, _P, _P),
     "srml_csr_xty_f64": (_P, _P, _P, _L, _P, _I, _P, _P),
+    # silhouette: (X, m, n, ld, mu, scale, r, M, k, ldm, t, N, labels, w, alpha, s, block slots, out) / segment
+    # sums (X, m, n, ld, perm, off, k, scale, w, sums, splits, ws) / (perm, off, k, w, r, N out, Psi out)
+    "srml_silhouette_f32": (_P, _L, _I, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _F, _P, _P, _P, _P),
+    "srml_silhouette_sums_f32": (_P, _L, _I, _L, _P, _P, _I, _P, _P, _P, _I, _P, _P),
+    "srml_silhouette_seg_scalars": (_P, _P, _I, _P, _P, _P, _P, _P),
     "srml_confusion_counts": (_P, _I, _P, _I, _L, _I, _P, _P),
     "srml_logloss_sum": (_P, _I, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_reg_moments": (_P, _I, _P, _I, _L, _P, _P),
