@@ -13,9 +13,9 @@ from typing import Any, List, Optional, Union
 
 import numpy as np
 
-from .core.dataframe import DataFrame, as_dataframe
-from .core.params import HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredictionCol, HasProbabilityCol, \
-    HasRawPredictionCol, Param, Params, TypeConverters, keyword_only
+from .core.dataframe import DataFrame, as_dataframe, vector_column_is_sparse, vector_column_to_csr
+from .core.params import HasEnableSparseDataOptim, HasFeaturesCol, HasFeaturesCols, HasLabelCol, HasPredictionCol, \
+    HasProbabilityCol, HasRawPredictionCol, Param, Params, TypeConverters, keyword_only
 from .metrics import ClassificationSummary, MulticlassMetrics, RegressionMetrics, RegressionSummary, binary_aupr, \
     binary_auc
 
@@ -148,9 +148,12 @@ class BinaryClassificationEvaluator(Evaluator, HasLabelCol, HasRawPredictionCol)
         return binary_auc(y, score)
 
 
-class ClusteringEvaluator(Evaluator, HasPredictionCol, HasFeaturesCol, HasFeaturesCols):
+class ClusteringEvaluator(Evaluator, HasPredictionCol, HasFeaturesCol, HasFeaturesCols, HasEnableSparseDataOptim):
     """Silhouette of a clustering (``pyspark.ml.evaluation.ClusteringEvaluator``): Spark's closed
-    form, every row scored against the k cluster summaries on the fused MFMA kernel."""
+    form, every row scored against the k cluster summaries on the fused MFMA kernel.
+    ``enable_sparse_data_optim=True`` (or ``None`` and a sparse first row) keeps a vector column CSR
+    and scores it on the CSR kernels without densifying; the default ``False`` densifies as before.
+    Array and multi-column features ignore the flag."""
     metricName = Param(Params._dummy(), "metricName", "metric name in evaluation (silhouette)",
                        typeConverter=TypeConverters.toString)
     distanceMeasure = Param(Params._dummy(), "distanceMeasure", "The distance measure. Supported options: "
@@ -160,11 +163,14 @@ class ClusteringEvaluator(Evaluator, HasPredictionCol, HasFeaturesCol, HasFeatur
     @keyword_only
     def __init__(self, *, predictionCol: str = "prediction", featuresCol: Union[str, List[str]] = "features",
                  metricName: str = "silhouette", distanceMeasure: str = "squaredEuclidean",
-                 weightCol: Optional[str] = None) -> None:
+                 weightCol: Optional[str] = None, enable_sparse_data_optim: Optional[bool] = False) -> None:
         super().__init__()
         self._setDefault(metricName="silhouette", distanceMeasure="squaredEuclidean", predictionCol="prediction",
-                         featuresCol="features")
+                         featuresCol="features", enable_sparse_data_optim=False)
         kw = {k: v for k, v in self._input_kwargs.items() if v is not None}
+        if "enable_sparse_data_optim" in self._input_kwargs:  # None is a value here: the first row decides
+            self._set(enable_sparse_data_optim=self._input_kwargs["enable_sparse_data_optim"])
+            kw.pop("enable_sparse_data_optim", None)
         fc = kw.pop("featuresCol", None)
         self._set(**kw)
         if fc is not None:
@@ -198,6 +204,12 @@ class ClusteringEvaluator(Evaluator, HasPredictionCol, HasFeaturesCol, HasFeatur
             return self._set(featuresCol=value)
         return self._set(featuresCols=list(value))
 
+    def _use_sparse(self, df: DataFrame, col: Optional[str]) -> bool:
+        if col is None or not df.is_vector(col):
+            return False
+        flag = self.getOrDefault("enable_sparse_data_optim")
+        return vector_column_is_sparse(df.column(col)) if flag is None else bool(flag)
+
     def _evaluate(self, dataset: Any) -> float:
         from .core.base import _dense_from_df
         from .models.silhouette import silhouette_score
@@ -208,11 +220,13 @@ class ClusteringEvaluator(Evaluator, HasPredictionCol, HasFeaturesCol, HasFeatur
         col = None if cols else self.getOrDefault("featuresCol")
         pc, wc = self.getOrDefault("predictionCol"), self.getWeightCol()
         df = _local(dataset, (cols or [col]) + [pc] + ([wc] if wc else []))
+        sparse = self._use_sparse(df, col)  # one decision for every partition
         parts = []
         for t in df.partitions:
             if t.num_rows == 0:
                 continue
             p = DataFrame([t])
-            parts.append((_dense_from_df(p, col, cols, np.float32), p.to_numpy(pc, np.float64),
+            X = vector_column_to_csr(p.column(col), np.float32) if sparse else _dense_from_df(p, col, cols, np.float32)
+            parts.append((X, p.to_numpy(pc, np.float64),
                           p.to_numpy(wc, np.float64) if wc else None))
         return silhouette_score(parts, self.getDistanceMeasure(), local_device())

@@ -5,18 +5,21 @@ weighted sums; squaredEuclidean then adds Psi', the centred second moments about
 mean, ``ops.silhouette_psi``). Pass 2 scores every row against the k summaries on the fused MFMA
 kernel (``ops.silhouette``) and adds (sum of w s, sum of w) per partition. The partitions are placed
 on the device once and stay resident between the passes: a pass over resident rows costs a
-fraction of their host-to-device copy.
+fraction of their host-to-device copy. A partition whose features are a ``scipy.sparse.csr_matrix``
+stays CSR on the device and takes the CSR kernels of the same three ops (``csrc/csr_silhouette.hip``).
 """
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
 from .. import ops
 
-Partition = Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]  # features (m, n), predictions (m), weights (m)
+# features (m, n) dense or scipy.sparse.csr_matrix, predictions (m), weights (m)
+Partition = Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]
 
 
 def _dense_ids(parts: List[Partition]) -> Tuple[List[Partition], List[np.ndarray], int]:
@@ -47,7 +50,9 @@ def silhouette_score(parts: List[Partition], measure: str, device: torch.device)
         raise ValueError("ClusteringEvaluator: distanceMeasure must be one of %s, got %r"
                          % (ops.SILHOUETTE_MEASURES, measure))
     kept, ids, k = _dense_ids(parts)
-    dev = [(to_device(np.ascontiguousarray(X, np.float32), device, torch.float32),
+    # a scipy CSR partition goes to the device as CSR (core.base.CSR) and is scored by the CSR kernels
+    dev = [(to_device(X.sorted_indices() if sp.issparse(X) else np.ascontiguousarray(X, np.float32), device,
+                      torch.float32),
             torch.from_numpy(lab).to(device),
             torch.from_numpy(w).to(device) if w is not None else None) for (X, _, w), lab in zip(kept, ids)]
     N = Y = None

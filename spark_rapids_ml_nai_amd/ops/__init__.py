@@ -5165,7 +5165,10 @@ def silhouette_sums(X: torch.Tensor, labels: torch.Tensor, k: int, weights: Opti
                     measure: str = "squaredEuclidean") -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-cluster (N fp64 [k] = sum of w, Y fp64 [k, n] = sum of w x; cosine: of w x / ||x||) of one
     block of rows; the summaries of several partitions add. Device: label-sorted segments summed in
-    fp64 in a fixed order (``srml_silhouette_sums_f32``)."""
+    fp64 in a fixed order (``srml_silhouette_sums_f32``). ``X`` may be a CSR (``core.base.CSR`` or any
+    object with ``indptr`` / ``indices`` / ``data`` / ``shape``): see ``_csr_sil_sums``."""
+    if _sil_is_csr(X):
+        return _csr_sil_sums(X, *_sil_args(X.data, labels, weights, measure), int(k), measure)
     lab, w = _sil_args(X, labels, weights, measure)
     m, n = X.shape
     if not _sil_native(X):
@@ -5203,7 +5206,14 @@ def silhouette_centre(N: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
 def silhouette_psi(X: torch.Tensor, labels: torch.Tensor, k: int, mu: torch.Tensor,
                    weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Psi' fp64 [k] = per-cluster sum of w ||x - mu||^2 of one block of rows (adds over partitions):
-    from the centred norms, never from an expanded sum of ||x||^2."""
+    from the centred norms, never from an expanded sum of ||x||^2. A CSR ``X`` takes the norms from
+    its non-zeros alone (``_csr_sil_rows``)."""
+    if _sil_is_csr(X):
+        lab, w = _sil_args(X.data, labels, weights, "squaredEuclidean")
+        r = _csr_sil_rows(X, mu)
+        if lab.numel() != r.numel() or (w is not None and w.numel() != r.numel()):
+            raise ValueError("silhouette_psi: labels / weights do not match the %d rows" % r.numel())
+        return _sil_seg_sum(lab, int(k), r if w is None else r * w)
     lab, w = _sil_args(X, labels, weights, "squaredEuclidean")
     if not _sil_native(X):
         r = ((X.double() - mu.double().to(X.device)) ** 2).sum(1)
@@ -5222,6 +5232,19 @@ def _sil_formula(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
                        torch.where(a > b, b / torch.where(a > b, a, one) - 1, torch.zeros_like(a)))
 
 
+def _sil_rows_from_d(d: torch.Tensor, lc: torch.Tensor, wc: torch.Tensor, N: torch.Tensor, live: torch.Tensor
+                     ) -> torch.Tensor:
+    """s of a chunk of rows from its fp64 (rows, k) distances to the clusters (clamped in place)."""
+    d.clamp_min_(0)
+    d[:, ~live] = math.inf
+    own = d.gather(1, lc.view(-1, 1)).view(-1)
+    b = d.scatter(1, lc.view(-1, 1), math.inf).min(1).values
+    Nl = N[lc]
+    scored = (wc > 0) & (Nl > wc)
+    a = own * Nl / torch.where(scored, Nl - wc, torch.ones_like(Nl))
+    return torch.where(scored, _sil_formula(a, b), torch.zeros_like(a))
+
+
 def silhouette(X: torch.Tensor, labels: torch.Tensor, k: int, weights: Optional[torch.Tensor] = None,
                measure: str = "squaredEuclidean", stats: Optional[Tuple[torch.Tensor, ...]] = None,
                rows_out: bool = False) -> Tuple[torch.Tensor, ...]:
@@ -5230,7 +5253,11 @@ def silhouette(X: torch.Tensor, labels: torch.Tensor, k: int, weights: Optional[
     cluster summaries merged over every partition (``silhouette_sums`` / ``silhouette_psi``; Psi' is
     unused for cosine), computed from ``X`` when absent. Device fp32 rows run the fused MFMA kernel
     (``srml_silhouette_f32``): no m x k matrix, no centred copy of X, bit-identical run to run.
-    Other inputs run in fp64 on row chunks."""
+    Other inputs run in fp64 on row chunks. A CSR ``X`` (see ``silhouette_sums``) with fp32 values on
+    the device runs ``srml_csr_silhouette_f32``, any other CSR an fp64 sparse product per row chunk;
+    neither densifies the rows."""
+    if _sil_is_csr(X):
+        return _csr_silhouette(X, *_sil_args(X.data, labels, weights, measure), int(k), measure, stats, rows_out)
     lab, w = _sil_args(X, labels, weights, measure)
     m, n = X.shape
     cos = measure == "cosine"
@@ -5267,14 +5294,7 @@ def silhouette(X: torch.Tensor, labels: torch.Tensor, k: int, weights: Optional[
                 d = 1.0 - V @ Mc.T
             else:
                 d = (V * V).sum(1).view(-1, 1) + tc.view(1, -1) - 2.0 * (V @ Mc.T)
-            d.clamp_min_(0)
-            d[:, ~live] = math.inf
-            own = d.gather(1, lc.view(-1, 1)).view(-1)
-            b = d.scatter(1, lc.view(-1, 1), math.inf).min(1).values
-            Nl = N[lc]
-            scored = (wc > 0) & (Nl > wc)
-            a = own * Nl / torch.where(scored, Nl - wc, torch.ones_like(Nl))
-            s[r0: r0 + step] = torch.where(scored, _sil_formula(a, b), torch.zeros_like(a))
+            s[r0: r0 + step] = _sil_rows_from_d(d, lc, wc, N, live)
         out = ((wd * s).sum(), sum_w)
         return out + (s.float(),) if rows_out else out
     X = X if X.stride(1) == 1 else X.contiguous()
@@ -5312,3 +5332,223 @@ def _sil_launch(X: torch.Tensor, k: int, operands: Tuple[Any, ...], rows_out: bo
                 native.ptr(rvec), M32.data_ptr(), k, M32.stride(0), native.ptr(tc32), Nc.data_ptr(), lab32.data_ptr(),
                 native.ptr(w), float(alpha), native.ptr(s), part.data_ptr(), out.data_ptr(), native.stream(dev))
     return out, s
+
+
+# ------------------------------------------------------------------------------------------
+# Silhouette on CSR rows (csrc/csr_silhouette.hip): the same closed form, centred without touching
+# the zeros. With M_c = m_c - mu, g_c = mu . M_c and r_i = ||x_i - mu||^2 taken from the non-zeros,
+# d(i, c) = r_i + t_c - 2 (x_i . M_c - g_c); the work per non-zero is one sparse dot against M.
+def _sil_is_csr(X: Any) -> bool:
+    return not isinstance(X, torch.Tensor) and hasattr(X, "indptr")
+
+
+def _csr_sil_native(A: Any) -> bool:
+    return A.data.is_cuda and A.data.dtype == torch.float32
+
+
+def csr_silhouette_config() -> Tuple[int, int, int, int]:
+    """(clusters per tile when kp > 64, non-zeros of a row staged in LDS, rows per block, table reads
+    in flight per lane) of ``srml_csr_silhouette_f32``, read from the library."""
+    cfg = native.lib().srml_csr_silhouette_config
+    return int(cfg(0)), int(cfg(1)), int(cfg(2)), int(cfg(3))
+
+
+def csr_silhouette_kp(k: int) -> int:
+    """Width of the scoring kernel's cluster table: k rounded up to 8, 16, 32 or a multiple of 64."""
+    return 8 if k <= 8 else 16 if k <= 16 else 32 if k <= 32 else (k + 63) // 64 * 64
+
+
+def _csr_sil_refused(name: str, rc: int, rows: int, k: int, kp: int) -> None:
+    if rc < 0:
+        raise ValueError("%s refused the launch (status %d: -1 grid overflow, -2 cluster count / padding) for %d "
+                         "rows, k=%d, kp=%d" % (name, rc, rows, k, kp))
+    if rc != 0:
+        raise RuntimeError("%s launch failed with HIP status %d" % (name, rc))
+
+
+def _sil_seg_sum(lab: torch.Tensor, k: int, v: Optional[torch.Tensor]) -> torch.Tensor:
+    """fp64 [k] per-label sums of the per-row fp64 scalars ``v`` (None: ones). Device: the fixed-order
+    segment fold of the dense path (``label_sort`` + ``srml_silhouette_seg_scalars``)."""
+    out = torch.empty(k, dtype=torch.float64, device=lab.device)
+    if not lab.is_cuda:
+        v = torch.ones(lab.shape[0], dtype=torch.float64) if v is None else v
+        return out.zero_().index_add_(0, lab.long(), v)
+    perm, off, _ = label_sort(lab, k)
+    native.call("srml_silhouette_seg_scalars", perm.data_ptr(), off.data_ptr(), k, native.ptr(None if v is None else _c(v)),
+                None, out.data_ptr(), None, native.stream(lab.device))
+    return out
+
+
+def _csr_sil_rows(A: Any, mu: Optional[torch.Tensor]) -> torch.Tensor:
+    """fp64 [m]: r_i = sum_nz (x_ij - mu_j)^2 + (||mu||^2 - sum_nz mu_j^2) = ||x_i - mu||^2 with x - mu
+    never formed, or ||x_i||^2 when ``mu`` is None (``srml_csr_silhouette_rows_f32``: a wave per row,
+    fp64, fixed order)."""
+    m = int(A.shape[0])
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    mud = None if mu is None else _c(mu.to(device=dev, dtype=torch.float64))
+    if mud is not None and mud.numel() != int(A.shape[1]):
+        raise ValueError("silhouette: a centre of %d values for %d features" % (mud.numel(), int(A.shape[1])))
+    mu2 = float((mud * mud).sum()) if mud is not None else 0.0
+    if not _csr_sil_native(A):
+        rows, v = _csr_km_rows(A, a, b), A.data[a:b].double()
+        if mud is None:
+            return torch.zeros(m, dtype=torch.float64, device=dev).index_add_(0, rows, v * v)
+        u = mud[A.indices[a:b].long()]
+        return torch.zeros(m, dtype=torch.float64, device=dev).index_add_(0, rows, (v - u) ** 2 - u * u) + mu2
+    out = torch.empty(m, dtype=torch.float64, device=dev)
+    indptr = _c(A.indptr)
+    for r0 in range(0, m, _CSR_KM_LAUNCH_ROWS):
+        r = min(_CSR_KM_LAUNCH_ROWS, m - r0)
+        rc = native.call_status("srml_csr_silhouette_rows_f32", indptr[r0:].data_ptr(), A.indices.data_ptr(),
+                                A.data.data_ptr(), r, native.ptr(mud), mu2, out[r0:].data_ptr(), native.stream(dev))
+        _csr_sil_refused("srml_csr_silhouette_rows_f32", rc, r, 0, 0)
+    return out
+
+
+def _csr_sil_cos_norms(A: Any, w: Optional[torch.Tensor]) -> torch.Tensor:
+    """fp64 ||x_i||^2 of the CSR rows (cosine); a zero row that carries weight is an error."""
+    sq = _csr_sil_rows(A, None)
+    if bool(((sq == 0) if w is None else (sq == 0) & (w > 0)).any()):
+        raise ValueError("silhouette: cosine distance is not defined for zero-length vectors")
+    return sq
+
+
+def _csr_sil_sums(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int, measure: str
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``silhouette_sums`` of CSR rows: Y[label][col] += f_i value over the non-zeros with the per-row
+    factor f_i = w_i (cosine: w_i / ||x_i||). Device fp32 values: ``srml_csr_silhouette_sums_f32``, one
+    fp64 atomic per non-zero, or in deterministic mode exact i64 fixed-point atomics scaled by
+    ``csr_fixed_scale(m, max|f| max|value|)`` (a bound of max|f_i value|) that repeat bit for bit. N
+    is a fixed-order segment fold. A k x n buffer past ``_CSR_KM_SUMS_BYTES`` (or the device's free
+    memory) raises ``ValueError``."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    if lab.numel() != m or (w is not None and w.numel() != m):
+        raise ValueError("silhouette_sums: labels / weights do not match the %d rows" % m)
+    need = k * n * 8
+    limit = _CSR_KM_SUMS_BYTES
+    if A.data.is_cuda and need <= limit:
+        limit = min(limit, int(torch.cuda.mem_get_info(dev)[0]))
+    if need > limit:
+        raise ValueError("silhouette_sums: the %d x %d fp64 cluster sums need %d bytes, more than the %d available; "
+                         "reduce k or the number of features" % (k, n, need, limit))
+    lab = _c(lab.to(torch.int32))
+    N = _sil_seg_sum(lab, k, w)
+    f = w
+    if measure == "cosine":
+        sq = _csr_sil_cos_norms(A, w)
+        f = torch.where(sq > 0, sq.rsqrt(), torch.zeros_like(sq))
+        f = f if w is None else f * w
+    Y = zeros((k, n), dtype=torch.float64, device=dev)
+    if m == 0 or b == a:
+        return N, Y
+    scale = 0.0
+    if deterministic():
+        scale = csr_fixed_scale(m, float(A.data[a:b].abs().max()) * (1.0 if f is None else float(f.max())))
+    if not _csr_sil_native(A):
+        rows = _csr_km_rows(A, a, b)
+        cell = lab.long()[rows] * n + A.indices[a:b].long()
+        v = A.data[a:b].double() if f is None else A.data[a:b].double() * f[rows]
+        if scale:
+            acc = torch.zeros(k * n, dtype=torch.int64, device=dev).index_add_(0, cell, torch.round(v * scale).long())
+            Y.copy_((acc.double() * (1.0 / scale)).view(k, n))
+        else:
+            Y.view(-1).index_add_(0, cell, v)
+        return N, Y
+    st = native.stream(dev)
+    native.call("srml_csr_silhouette_sums_f32", _c(A.indptr).data_ptr(), A.indices.data_ptr(), A.data.data_ptr(), m, n,
+                b - a, lab.data_ptr(), k, native.ptr(None if f is None else _c(f)), scale, Y.data_ptr(), st)
+    if scale:
+        native.call("srml_csr_cluster_sums_finish", Y.data_ptr(), k * n, 1.0 / scale, st)
+    return N, Y
+
+
+def _csr_silhouette(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int, measure: str,
+                    stats: Optional[Tuple[torch.Tensor, ...]], rows_out: bool) -> Tuple[torch.Tensor, ...]:
+    """``silhouette`` of CSR rows. The summaries become M (k x n: m_c - mu, cosine m_c; fp64, rounded
+    once to fp32 for the kernel), g_c = mu . M_c from those same M and t_c = Psi'_c / N_c (+inf for an
+    empty cluster); the rows give r_i (``_csr_sil_rows``). Device fp32 values: the transposed table
+    MT (n x kp, ``csr_silhouette_kp``; past ``_CSR_KM_CT_BYTES`` or the free memory: ``ValueError``) and
+    ``srml_csr_silhouette_f32`` on at most ``_CSR_KM_LAUNCH_ROWS`` rows per launch. Otherwise an fp64
+    sparse product per chunk of rows (rows x k), never a dense rows x n array."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    cos = measure == "cosine"
+    if lab.numel() != m or (w is not None and w.numel() != m):
+        raise ValueError("silhouette: labels / weights do not match the %d rows" % m)
+    if m == 0:
+        z = torch.zeros((), dtype=torch.float64, device=dev)
+        return (z, z.clone(), torch.empty(0, dtype=torch.float32, device=dev)) if rows_out else (z, z.clone())
+    if stats is None:
+        N, Y = _csr_sil_sums(A, lab, w, k, measure)
+        psi = None if cos else silhouette_psi(A, lab, k, silhouette_centre(N, Y), w)
+    else:
+        N, Y = stats[0].to(dev), stats[1].to(dev)
+        psi = None if cos else stats[2].to(dev)
+    if N.shape != (k,) or Y.shape != (k, n) or (psi is not None and psi.shape != (k,)):
+        raise ValueError("silhouette: the summaries do not match k = %d clusters of %d features" % (k, n))
+    live = N > 0
+    if int(live.sum()) < 2:
+        raise ValueError("silhouette: Number of clusters must be greater than one")
+    use_kernel = _csr_sil_native(A)
+    kp = csr_silhouette_kp(k) if use_kernel else k
+    if use_kernel:
+        need = n * kp * 4
+        limit = min(_CSR_KM_CT_BYTES, int(torch.cuda.mem_get_info(dev)[0]))
+        if need > limit:
+            raise ValueError("silhouette: the %d x %d transposed cluster table (k = %d padded to %d) needs %d bytes, "
+                             "more than the %d available; reduce k or the number of features"
+                             % (n, kp, k, kp, need, limit))
+    Nd = torch.where(live, N, torch.ones_like(N))
+    sum_w = w.sum() if w is not None else torch.tensor(float(m), dtype=torch.float64, device=dev)
+    mu = None if cos else silhouette_centre(N, Y).double()
+    Mc = Y.double() / Nd.view(-1, 1)
+    Mc = (Mc if cos else Mc - mu) * live.view(-1, 1)
+    if use_kernel:
+        Mc = Mc.float()
+    inf = torch.full((kp,), math.inf, dtype=torch.float64, device=dev)
+    tc = inf.clone()
+    tc[:k] = torch.where(live, torch.zeros_like(N) if cos else psi.double() / Nd, inf[:k])
+    g = torch.zeros(kp, dtype=torch.float64, device=dev)
+    if not cos:
+        g[:k] = Mc.double() @ mu
+    rv = _csr_sil_cos_norms(A, w) if cos else _csr_sil_rows(A, mu)
+    if not use_kernel:
+        McT = _c(Mc.t())
+        s = torch.empty(m, dtype=torch.float64, device=dev)
+        wd = w if w is not None else torch.ones(m, dtype=torch.float64, device=dev)
+        step = max(1, _SIL_CHUNK_ELEMS // max(k, 1))
+        for r0 in range(0, m, step):
+            r1 = min(m, r0 + step)
+            S = _csr_block(A, a, b, r0, r1) @ McT
+            rc = rv[r0:r1].view(-1, 1)
+            if cos:
+                d = 1.0 - S * torch.where(rc > 0, rc.rsqrt(), torch.zeros_like(rc))
+            else:
+                d = rc + tc.view(1, -1) - 2.0 * (S - g.view(1, -1))
+            s[r0:r1] = _sil_rows_from_d(d, lab[r0:r1].long(), wd[r0:r1], N, live)
+        out = ((wd * s).sum(), sum_w)
+        return out + (s.float(),) if rows_out else out
+    MT = zeros((n, kp), dtype=torch.float32, device=dev)
+    MT[:, :k] = Mc.t()
+    lab32, Nc, indptr, st = _c(lab.to(torch.int32)), _c(N.double()), _c(A.indptr), native.stream(dev)
+    s = torch.empty(m, dtype=torch.float32, device=dev) if rows_out else None
+    rpb = csr_silhouette_config()[2]
+    step = _CSR_KM_LAUNCH_ROWS // rpb * rpb
+    part = torch.empty((min(m, step) + rpb - 1) // rpb, dtype=torch.float64, device=dev)
+    outs = torch.empty((m + step - 1) // step, dtype=torch.float64, device=dev)
+    for i, r0 in enumerate(range(0, m, step)):
+        r = min(step, m - r0)
+        rc = native.call_status("srml_csr_silhouette_f32", indptr[r0:].data_ptr(), A.indices.data_ptr(),
+                                A.data.data_ptr(), r, MT.data_ptr(), k, kp, g.data_ptr(), tc.data_ptr(), Nc.data_ptr(),
+                                rv[r0:].data_ptr(), lab32[r0:].data_ptr(), None if w is None else w[r0:].data_ptr(),
+                                int(cos), None if s is None else s[r0:].data_ptr(), part.data_ptr(),
+                                outs[i:].data_ptr(), st)
+        _csr_sil_refused("srml_csr_silhouette_f32", rc, r, k, kp)
+    sws = outs[0]
+    for i in range(1, outs.numel()):  # the launches in order
+        sws = sws + outs[i]
+    return (sws, sum_w, s) if rows_out else (sws, sum_w)

@@ -250,6 +250,12 @@ SIGNATURES: Dict[str, Tuple[Any, ...]] = {
     "srml_silhouette_f32": (_P, _L, _I, _L, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P, _F, _P, _P, _P, _P),
     "srml_silhouette_sums_f32": (_P, _L, _I, _L, _P, _P, _I, _P, _P, _P, _I, _P, _P),
     "srml_silhouette_seg_scalars": (_P, _P, _I, _P, _P, _P, _P, _P),
+    # silhouette on CSR rows: (row offsets, indices, values, rows), then mu, ||mu||^2, out / n, nnz, labels, k, f,
+    # fixed-point scale (0: fp64 atomics), sums / MT, k, kp, g, t, N, r, labels, w, cosine, s, block slots, out
+    "srml_csr_silhouette_config": (_I,),
+    "srml_csr_silhouette_rows_f32": (_P, _P, _P, _L, _P, _D, _P, _P),
+    "srml_csr_silhouette_sums_f32": (_P, _P, _P, _L, _I, _L, _P, _I, _P, _D, _P, _P),
+    "srml_csr_silhouette_f32": (_P, _P, _P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P),
     "srml_confusion_counts": (_P, _I, _P, _I, _L, _I, _P, _P),
     "srml_logloss_sum": (_P, _I, _L, _I, _L, _P, _I, _D, _P, _P),
     "srml_reg_moments": (_P, _I, _P, _I, _L, _P, _P),

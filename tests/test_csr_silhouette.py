@@ -1,0 +1,182 @@
+"""Silhouette of CSR rows (ops.silhouette* on a CSR, ClusteringEvaluator(enable_sparse_data_optim)) against
+the direct O(m^2) definition on the fp32 values densified on the columns that occur. This file runs
+the fp64 route; test_csr_silhouette_gpu.py holds the kernels to the bound of ``bounds`` (docs/coverage.md,
+"CSR silhouette: contract and measured error"), u = 2^-24:
+
+  eps(i, c) = 2 (nnz_i + 8) u ||x_i|| ||M_c|| + (nnz_i + n + 16) 2^-53 (||x_i|| + ||mu|| + ||M_c|| + sqrt t_c)^2
+  cosine: ||x_i|| = 1, t = 0, mu = 0 above, plus 3 u ||m_c||
+  |s^_i - s_i| <= (eps(i, own) N / (N - w) + max_c eps(i, c)) / max(a_i, b_i) + 6 u
+  |score^ - score| <= weighted mean of the row bounds + m 2^-53
+"""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import torch
+
+from spark_rapids_ml_nai_amd import ops
+from spark_rapids_ml_nai_amd.core.base import CSR
+from spark_rapids_ml_nai_amd.core.dataframe import DataFrame
+from spark_rapids_ml_nai_amd.evaluation import ClusteringEvaluator
+from test_silhouette import oracle
+
+U = 2.0 ** -24
+TOL = 1e-10  # fp64 route, as in test_silhouette.py
+
+
+def make_case(m, k, n, nnz=None, measure="squaredEuclidean", weighted=False, seed=0):
+    """scipy CSR (fp32) of m rows on ids {0, 1, k-2, k-1} (a singleton id in between when k > 4, every
+    other id empty): unit-scale values on random columns of a pool of at most 640 of the n columns, and
+    10 (j + 1) on the home column of the row's cluster j, so that the supports are partly disjoint
+    and the clusters about 10 apart. ``nnz``: the row lengths, cycled (default 1 .. 12)."""
+    rng = np.random.default_rng(seed)
+    used = sorted({0, 1, k - 2, k - 1} & set(range(k)))
+    lab = np.array(used)[np.arange(m) % len(used)]
+    if k > 4 and m > 8:
+        lab[m // 2] = k // 2
+    pos = {c: j for j, c in enumerate(used + [k // 2])}
+    pool = np.sort(rng.choice(n, min(n, 640), replace=False))
+    indptr, indices, data = [0], [], []
+    for i in range(m):
+        z = min(len(pool), int(nnz[i % len(nnz)]) if nnz is not None else int(rng.integers(1, 13)))
+        j = pos[lab[i]]
+        home = pool[j % len(pool)]
+        cols = np.sort(np.append(rng.choice(pool[pool != home], z - 1, replace=False), home)) if z else np.zeros(0, int)
+        vals = rng.standard_normal(len(cols)) + np.where(cols == home, 10.0 * (j + 1), 0.0)
+        indices.extend(cols)
+        data.extend(vals)
+        indptr.append(len(indices))
+    A = sp.csr_matrix((np.array(data, np.float32), np.array(indices, np.int32), np.array(indptr, np.int64)), (m, n))
+    w = None
+    if weighted:
+        w = rng.uniform(0.5, 2.0, m)
+        w[m // 3] = 0.0
+    return A, lab, w
+
+
+def to_csr(A, device):
+    return CSR(torch.from_numpy(A.indptr.astype(np.int64)).to(device),
+               torch.from_numpy(A.indices.astype(np.int32)).to(device), torch.from_numpy(A.data).to(device), A.shape)
+
+
+def bounds(A, lab, w, measure, exact=False):
+    """(s, w, row bounds) of the case from the oracle alone; a generic case has no scored row whose
+    max(a, b) is within the error of a and b."""
+    m, n = A.shape
+    X = np.asarray(A[:, np.unique(A.indices)].todense(), np.float64)  # an all-zero column adds nothing
+    s, a, b = oracle(X, lab, w, measure)
+    w = np.ones(m) if w is None else w
+    cos = measure == "cosine"
+    nz, xn = np.diff(A.indptr), np.linalg.norm(X, axis=1)
+    V = X / np.where(xn > 0, xn, 1.0)[:, None] if cos else X
+    mu = np.zeros(X.shape[1]) if cos else (w @ V) / w.sum()
+    ids = np.unique(lab[w > 0])
+    W = np.stack([w * (lab == c) for c in ids], 1)
+    N, own = W.sum(0), np.searchsorted(ids, lab).clip(max=len(ids) - 1)
+    Mn = np.linalg.norm((W.T @ V) / N[:, None] - mu, axis=1)
+    t = np.zeros(len(ids)) if cos else (W.T @ ((V - mu) ** 2).sum(1)) / N
+    xs = np.ones(m) if cos else xn
+    eps = 2 * (nz + 8)[:, None] * U * xs[:, None] * Mn[None, :] + (nz + n + 16)[:, None] * 2.0 ** -53 * (
+        xs[:, None] + np.linalg.norm(mu) + Mn[None, :] + np.sqrt(t)[None, :]) ** 2 + (3 * U * Mn[None, :] if cos else 0.0)
+    scored = (w > 0) & (N[own] > w)
+    if exact:  # lattice: every quantity is exact, only the formula and the fp32 store round
+        return s, w, np.where(scored, 6 * U, 0.0)
+    da = np.where(scored, eps[np.arange(m), own] * N[own] / np.where(scored, N[own] - w, 1.0), 0.0)
+    db = np.where(scored, eps.max(1), 0.0)
+    assert (np.maximum(a, b)[scored] > (da + db)[scored]).all(), "case is not generic"
+    return s, w, np.where(scored, (da + db) / np.where(scored, np.maximum(a, b), 1.0) + 6 * U, 0.0)
+
+
+def check(A, lab, w, k, measure, device="cpu", exact=False, head=None):
+    """Score the CSR on ``device`` (``head``: only its first rows, as one block of a partitioned set,
+    against the summaries of all rows) and hold rows and sums to the bound; returns the rows."""
+    h = A.shape[0] if head is None else head
+    Ad, labd = to_csr(A, device), torch.from_numpy(lab).to(device)
+    wd = None if w is None else torch.from_numpy(w).to(device)
+    stats = None
+    if head is not None:
+        N, Y = ops.silhouette_sums(Ad, labd, k, wd, measure)
+        stats = (N, Y, None if measure == "cosine" else ops.silhouette_psi(Ad, labd, k, ops.silhouette_centre(N, Y), wd))
+    sws, sw, rows = ops.silhouette(to_csr(A[:h], device), labd[:h], k, None if wd is None else wd[:h], measure,
+                                   stats=stats, rows_out=True)
+    s, w, bound = (x[:h] for x in bounds(A, lab, w, measure, exact))
+    err = np.abs(rows.cpu().numpy().astype(np.float64) - s)
+    score, got = (w * s).sum() / w.sum(), float(sws) / float(sw)
+    sbound = (w * bound).sum() / w.sum() + h * 2.0 ** -53
+    print("worst row err/bound %.3f  score err/bound %.3f" % ((err[bound > 0] / bound[bound > 0]).max(initial=0.0),
+                                                              abs(got - score) / sbound))
+    assert (err <= bound).all(), (err - bound).max()  # an unscored row (bound 0) is exactly 0
+    assert abs(float(sw) - w.sum()) <= 1e-12 * w.sum()
+    assert abs(got - score) <= sbound
+    return rows.cpu()
+
+
+def lattice(k):
+    """The points of test_silhouette's tie case on columns 3 and 50 of 100 ((0, 0) is an empty row),
+    cluster sizes 2 on the first, middle and last ids."""
+    pts = [(0, 0), (2, 0), (0, 2), (0, -2), (8, 8), (8, 8), (8, 8), (8, 8)]
+    rows = [[(c, v) for c, v in zip((3, 50), p) if v] for p in pts]
+    A = sp.csr_matrix((np.array([v for r in rows for _, v in r], np.float32),
+                       np.array([c for r in rows for c, _ in r], np.int32),
+                       np.cumsum([0] + [len(r) for r in rows]).astype(np.int64)), (8, 100))
+    return A, np.array([0, 0, k // 2, k // 2, 1, 1, k - 1, k - 1])
+
+
+@pytest.fixture(autouse=True)
+def _cpu(monkeypatch):
+    monkeypatch.setenv("SRML_FORCE_CPU", "1")
+
+
+@pytest.mark.parametrize("measure", ("squaredEuclidean", "cosine"))
+@pytest.mark.parametrize("weighted", (False, True))
+@pytest.mark.parametrize("dtype", (np.float32, np.float64))
+def test_fp64_route_matches_definition(measure, weighted, dtype):
+    A, lab, w = make_case(129, 9, 100, None if measure == "cosine" else [0, 1, 5, 100, 7], measure, weighted)
+    check(A, lab, w, 9, measure, head=None if weighted else 2)
+    s, _, _ = oracle(np.asarray(A.todense(), np.float64), lab, w, measure)
+    ww = np.ones(129) if w is None else w
+    sws, sw, rows = ops.silhouette(to_csr(A.astype(dtype), "cpu"), torch.from_numpy(lab), 9,
+                                   None if w is None else torch.from_numpy(w), measure, rows_out=True)
+    assert np.abs(rows.numpy() - s).max() <= U + TOL  # the rows come back as fp32
+    assert abs(float(sws) / float(sw) - (ww * s).sum() / ww.sum()) <= TOL
+
+
+def test_lattice_ties_are_exact_zero():
+    A, lab = lattice(4)
+    rows = check(A, lab, None, 4, "squaredEuclidean", exact=True)
+    assert (rows[[0, 4, 5, 6, 7]] == 0).all()
+
+
+@pytest.mark.parametrize("measure", ("squaredEuclidean", "cosine"))
+def test_evaluator_sparse_param(measure):
+    A, lab, w = make_case(60, 3, 40, measure=measure, weighted=True)
+    s, _, _ = oracle(np.asarray(A.todense(), np.float64), lab, w, measure)
+    score = (w * s).sum() / w.sum()
+    for parts in (1, 3):  # a scipy matrix becomes a column of sparse vectors
+        df = DataFrame.from_numpy(A, extra={"prediction": 3.0 * lab, "w": w}, num_partitions=parts)
+        for flag in (True, None):
+            ev = ClusteringEvaluator(distanceMeasure=measure, weightCol="w", enable_sparse_data_optim=flag)
+            assert ev.getOrDefault("enable_sparse_data_optim") is flag
+            assert abs(ev.evaluate(df) - score) <= TOL
+    dense, off = (ClusteringEvaluator(distanceMeasure=measure, weightCol="w", **kw)
+                  for kw in ({}, {"enable_sparse_data_optim": False}))
+    assert dense.getOrDefault("enable_sparse_data_optim") is False and dense.evaluate(df) == off.evaluate(df)
+    assert abs(dense.evaluate(df) - score) <= TOL
+
+
+def test_errors_before_any_work(monkeypatch):
+    A, lab, w = make_case(12, 2, 30, [3])
+    labt = torch.from_numpy(lab)
+    Z = A.copy()
+    Z.data[Z.indptr[2]: Z.indptr[3]] = 0.0
+    with pytest.raises(ValueError, match="zero-length"):
+        ops.silhouette(to_csr(Z, "cpu"), labt, 2, None, "cosine")
+    wz = torch.tensor([1.0, 1, 0] + [1] * 9, dtype=torch.float64)  # the zero row carries no weight: legal, scores 0
+    assert ops.silhouette(to_csr(Z, "cpu"), labt, 2, wz, "cosine", rows_out=True)[2][2] == 0
+    for bad in ("unsorted", "range"):
+        B = to_csr(A, "cpu")
+        B.indices[[0, 1]] = B.indices[[1, 0]] if bad == "unsorted" else 30
+        with pytest.raises(ValueError, match="CSR column"):
+            ops.silhouette_sums(B, labt, 2)
+    monkeypatch.setattr(ops, "_CSR_KM_SUMS_BYTES", 64)
+    with pytest.raises(ValueError, match="cluster sums need"):
+        ops.silhouette(to_csr(A, "cpu"), labt, 2)
