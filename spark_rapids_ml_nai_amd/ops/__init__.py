@@ -3798,6 +3798,26 @@ def _csr_block_row_sums(indptr: torch.Tensor, vals: torch.Tensor, m: int) -> tor
     return zeros(m, dtype=torch.float64, device=vals.device).index_add_(0, rows, vals[a: a + rows.numel()].double())
 
 
+def _csr_structure(indptr: torch.Tensor, indices: torch.Tensor, m: int, n: int) -> Tuple[int, int]:
+    """The (first, last) offset of the m rows after the structural check the CSR kernels rely on
+    (``ValueError`` otherwise): row offsets monotone inside the index array, every column index in
+    [0, n), indices strictly increasing within each row (so no duplicates)."""
+    a, b = (int(indptr[0]), int(indptr[-1])) if m else (0, 0)
+    if a < 0 or b > indices.numel() or b < a or bool((indptr[1:] < indptr[:-1]).any()):
+        raise ValueError("CSR row offsets are not a monotone sequence inside the index array")
+    idx = indices[a:b]
+    if idx.numel():
+        if bool(((idx < 0) | (idx >= n)).any()):
+            raise ValueError("CSR column index out of range [0, %d)" % n)
+        rising = idx[1:] > idx[:-1]
+        starts = indptr[1:-1] - a  # first non-zero of rows 1 .. m - 1; equal to a neighbour's for empty rows
+        starts = starts[(starts > 0) & (starts < idx.numel())]
+        rising[starts - 1] = True  # a row's first index follows another row's last: no order between them
+        if not bool(rising.all()):
+            raise ValueError("CSR column indices must be strictly increasing within each row")
+    return a, b
+
+
 def csr_prepare(A: Any, metric: str) -> CSRRows:
     """The rows of the CSR ``A`` (indptr int64, indices int32, data, shape; ``indptr`` may be a
     slice of a larger matrix's row offsets) prepared for ``metric``:
@@ -3822,19 +3842,7 @@ def csr_prepare(A: Any, metric: str) -> CSRRows:
         raise ValueError("inconsistent CSR arrays")
     if not data.is_floating_point():
         data = data.float()
-    a, b = (int(indptr[0]), int(indptr[-1])) if m else (0, 0)
-    if a < 0 or b > indices.numel() or b < a or bool((indptr[1:] < indptr[:-1]).any()):
-        raise ValueError("CSR row offsets are not a monotone sequence inside the index array")
-    idx = indices[a:b]
-    if idx.numel():
-        if bool(((idx < 0) | (idx >= n)).any()):
-            raise ValueError("CSR column index out of range [0, %d)" % n)
-        rising = idx[1:] > idx[:-1]
-        starts = indptr[1:-1] - a  # first non-zero of rows 1 .. m - 1; equal to a neighbour's for empty rows
-        starts = starts[(starts > 0) & (starts < idx.numel())]
-        rising[starts - 1] = True  # a row's first index follows another row's last: no order between them
-        if not bool(rising.all()):
-            raise ValueError("CSR column indices must be strictly increasing within each row")
+    a, b = _csr_structure(indptr, indices, m, n)
     vals = data[a:b]
     aux = None
     if name == "hellinger":
@@ -4291,10 +4299,10 @@ def nnd_join(Q_rows: torch.Tensor, I: torch.Tensor, pos: torch.Tensor, perm: Opt
 
 # ------------------------------------------------------------------------------------------
 # KMeans on CSR rows against dense centres (csrc/csr_kmeans.hip)
-# dispatch constants of csrc/csr_kmeans.hip (srml_csr_kmeans_config returns the same three)
-CSR_KM_TK = 256             # centres per pass of the search: 64 lanes x 4 accumulators (KM_TK)
-CSR_KM_STAGE = 512          # non-zeros of a row staged in LDS and re-used across centre tiles (KM_STAGE)
-CSR_KM_ROWS = 4             # rows (waves) per block (KM_ROWS)
+# dispatch constants of csrc/csr_table.h (srml_csr_kmeans_config returns the same three)
+CSR_KM_TK = 256             # centres per pass of the search: 64 lanes x 4 accumulators (CSR_TK)
+CSR_KM_STAGE = 512          # non-zeros of a row staged in LDS and re-used across centre tiles (CSR_STAGE)
+CSR_KM_ROWS = 4             # rows (waves) per block (CSR_ROWS)
 _CSR_KM_LAUNCH_ROWS = 1 << 22   # rows of one search launch (16.7M blocks of 4 rows is the grid's limit)
 _CSR_KM_SUMS_BYTES = 16 << 30   # the k x n fp64 cluster-sum buffer a fit may ask for
 _CSR_KM_CT_BYTES = 8 << 30      # the transposed, 64-padded centre table (n x kp) of the search
@@ -4319,19 +4327,7 @@ def _csr_km_check(A: Any) -> Tuple[int, int]:
     done = getattr(A, "_srml_km_checked", None)
     if done is not None:
         return done
-    a, b = (int(indptr[0]), int(indptr[-1])) if m else (0, 0)
-    if a < 0 or b > indices.numel() or b < a or (m and bool((indptr[1:] < indptr[:-1]).any())):
-        raise ValueError("CSR row offsets are not a monotone sequence inside the index array")
-    idx = indices[a:b]
-    if idx.numel():
-        if bool(((idx < 0) | (idx >= n)).any()):
-            raise ValueError("CSR column index out of range [0, %d)" % n)
-        rising = idx[1:] > idx[:-1]
-        starts = indptr[1:-1] - a
-        starts = starts[(starts > 0) & (starts < idx.numel())]
-        rising[starts - 1] = True  # a row's first index follows another row's last: no order between them
-        if not bool(rising.all()):
-            raise ValueError("CSR column indices must be strictly increasing within each row")
+    a, b = _csr_structure(indptr, indices, m, n)
     try:
         A._srml_km_checked = (a, b)
     except AttributeError:
@@ -4343,6 +4339,88 @@ def _csr_km_rows(A: Any, a: int, b: int) -> torch.Tensor:
     """Row number of every non-zero a .. b of the block."""
     m = int(A.shape[0])
     return torch.repeat_interleave(torch.arange(m, device=A.indptr.device), A.indptr[1:] - A.indptr[:-1])
+
+
+def _csr_table_budget(who: str, what: str, n: int, kp: int, k: int, esize: int, dev: torch.device) -> None:
+    """``ValueError`` where the n x kp transposed table of a one-wave-per-row kernel is past
+    ``_CSR_KM_CT_BYTES`` or the device's free memory."""
+    need = n * kp * esize
+    limit = min(_CSR_KM_CT_BYTES, int(torch.cuda.mem_get_info(dev)[0]))
+    if need > limit:
+        raise ValueError("%s: the %d x %d transposed %s table (k = %d padded to %d) needs %d bytes, more than the %d "
+                         "available; reduce k or the number of features" % (who, n, kp, what, k, kp, need, limit))
+
+
+def _csr_refused(name: str, what: str, rc: int, rows: int, k: int, kp: int) -> None:
+    """A non-zero status of a one-wave-per-row launch: ``ValueError`` for the kernel's own refusals
+    (negative), ``RuntimeError`` for a HIP error."""
+    if rc < 0:
+        raise ValueError("%s refused the launch (status %d: -1 grid overflow, -2 %s count / padding) for %d rows, "
+                         "k=%d, kp=%d" % (name, rc, what, rows, k, kp))
+    if rc != 0:
+        raise RuntimeError("%s launch failed with HIP status %d" % (name, rc))
+
+
+def _csr_row_chunks(m: int, rpb: int) -> Iterator[Tuple[int, int]]:
+    """(first row, rows) of the launches over m rows: at most ``_CSR_KM_LAUNCH_ROWS`` each, rounded
+    down to the rows per block so that every launch but the last fills its blocks."""
+    step = max(rpb, int(_CSR_KM_LAUNCH_ROWS) // rpb * rpb)
+    for r0 in range(0, m, step):
+        yield r0, min(step, m - r0)
+
+
+def _csr_label_sums(who: str, A: Any, lab: torch.Tensor, k: int, f: Optional[torch.Tensor], vmax: Optional[float],
+                    out: Optional[torch.Tensor], kernel: Optional[str]) -> torch.Tensor:
+    """fp64 [k, n]: sums[label][col] += f_i value over the non-zeros of the checked CSR ``A`` (``f``:
+    per-row fp64 factors, None for 1; ``lab``: int32 on the values' device, rows with a label outside
+    [0, k) are ignored). ``kernel``: the entry point (``srml_csr_cluster_sums_*``, or
+    ``srml_csr_silhouette_sums_f32``, which takes ``f``), one fp64 atomic per non-zero; None for the
+    torch form. Deterministic mode: f value is scaled by ``csr_fixed_scale(m, max|f| max|value|)``
+    (``vmax``: max|value| where the caller has it), rounded to an integer and added with i64 atomics
+    — integer addition is exact in any order — then converted to fp64 once. ``out``: written there
+    (zeroed here). A k x n buffer of its own past ``_CSR_KM_SUMS_BYTES`` (or the device's free
+    memory) raises ``ValueError``; ``who`` opens the messages."""
+    m, n = int(A.shape[0]), int(A.shape[1])
+    a, b = _csr_km_check(A)
+    dev = A.data.device
+    need = k * n * 8
+    limit = _CSR_KM_SUMS_BYTES
+    if out is None and A.data.is_cuda and need <= limit:
+        limit = min(limit, int(torch.cuda.mem_get_info(dev)[0]))
+    if need > limit and out is None:
+        raise ValueError("%s: the %d x %d fp64 cluster sums need %d bytes, more than the %d available; "
+                         "reduce k or the number of features" % (who, k, n, need, limit))
+    if out is not None:
+        if out.shape != (k, n) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous fp64 (%d, %d) tensor on %s" % (who, k, n, dev))
+        sums = zero_(out)
+    else:
+        sums = zeros((k, n), dtype=torch.float64, device=dev)
+    if m == 0 or b == a or k == 0 or n == 0:
+        return sums
+    scale = 0.0
+    if deterministic():
+        vmax = float(A.data[a:b].abs().max()) if vmax is None else float(vmax)
+        scale = csr_fixed_scale(m, vmax if f is None else vmax * float(f.abs().max()))
+    if kernel is None:
+        rows = _csr_km_rows(A, a, b)
+        rl = lab.long()[rows]
+        ok = (rl >= 0) & (rl < k)
+        cell = rl[ok] * n + A.indices[a:b].long()[ok]
+        v = (A.data[a:b].double() if f is None else A.data[a:b].double() * f[rows])[ok]
+        if scale:
+            acc = torch.zeros(k * n, dtype=torch.int64, device=dev).index_add_(0, cell, torch.round(v * scale).long())
+            sums.copy_((acc.double() * (1.0 / scale)).view(k, n))
+        else:
+            sums.view(-1).index_add_(0, cell, v)
+        return sums
+    st = native.stream(dev)
+    factor = () if kernel.startswith("srml_csr_cluster_sums") else (native.ptr(None if f is None else _c(f)),)
+    native.call(kernel, _c(A.indptr).data_ptr(), A.indices.data_ptr(), A.data.data_ptr(), m, n, b - a, lab.data_ptr(), k,
+                *factor, scale, sums.data_ptr(), st)
+    if scale:
+        native.call("srml_csr_cluster_sums_finish", sums.data_ptr(), k * n, 1.0 / scale, st)
+    return sums
 
 
 def csr_nearest_centroid(A: Any, C: torch.Tensor,
@@ -4394,12 +4472,7 @@ def csr_nearest_centroid(A: Any, C: torch.Tensor,
     key = ("CT", n, kp, T, dev)
     CT = ws.get(key) if ws is not None else None
     if CT is None:
-        need = n * kp * A.data.element_size()
-        limit = min(_CSR_KM_CT_BYTES, int(torch.cuda.mem_get_info(dev)[0]))
-        if need > limit:
-            raise ValueError("csr_nearest_centroid: the %d x %d transposed centre table (k = %d padded to %d) needs %d "
-                             "bytes, more than the %d available; reduce k or the number of features"
-                             % (n, kp, k, kp, need, limit))
+        _csr_table_budget("csr_nearest_centroid", "centre", n, kp, k, A.data.element_size(), dev)
         CT = torch.empty((n, kp), dtype=T, device=dev)
         if ws is not None:
             ws[key] = CT
@@ -4407,17 +4480,11 @@ def csr_nearest_centroid(A: Any, C: torch.Tensor,
     native.call("srml_csr_centres_transpose_" + _sfx(A), _c(Cd).data_ptr(), k, n, kp, CT.data_ptr(), st)
     cnp = torch.full((kp,), float("inf"), dtype=T, device=dev)
     cnp[:k] = cn
-    step = max(CSR_KM_ROWS, int(_CSR_KM_LAUNCH_ROWS) // CSR_KM_ROWS * CSR_KM_ROWS)
-    for r0 in range(0, m, step):
-        r = min(step, m - r0)
+    for r0, r in _csr_row_chunks(m, CSR_KM_ROWS):
         rc = native.call_status("srml_csr_nearest_" + _sfx(A), indptr[r0:].data_ptr(), A.indices.data_ptr(),
                                 A.data.data_ptr(), r, CT.data_ptr(), cnp.data_ptr(), k, kp, labels[r0:].data_ptr(),
                                 d2[r0:].data_ptr(), st)
-        if rc < 0:
-            raise ValueError("srml_csr_nearest refused the launch (status %d: -1 grid overflow, -2 centre count / "
-                             "padding) for %d rows, k=%d, kp=%d" % (rc, r, k, kp))
-        if rc != 0:
-            raise RuntimeError("srml_csr_nearest launch failed with HIP status %d" % rc)
+        _csr_refused("srml_csr_nearest", "centre", rc, r, k, kp)
     return labels, d2
 
 
@@ -4443,48 +4510,14 @@ def csr_cluster_sums(A: Any, labels: torch.Tensor, k: int, out: Optional[torch.T
     values' device): the sums are written there (zeroed here). ``vmax``: max|value| of ``A`` when the
     caller already has it (a fit reads it back once, not per iteration). A k x n buffer past ``_CSR_KM_SUMS_BYTES`` (or
     the device's free memory) raises ``ValueError``."""
-    m, n = int(A.shape[0]), int(A.shape[1])
-    k = int(k)
-    a, b = _csr_km_check(A)
-    dev = A.data.device
+    m, k = int(A.shape[0]), int(k)
+    _csr_km_check(A)
     if labels.numel() != m:
         raise ValueError("csr_cluster_sums: %d labels for %d rows" % (labels.numel(), m))
-    need = k * n * 8
-    limit = _CSR_KM_SUMS_BYTES
-    if out is None and A.data.is_cuda and need <= limit:
-        limit = min(limit, int(torch.cuda.mem_get_info(dev)[0]))
-    if need > limit and out is None:
-        raise ValueError("csr_cluster_sums: the %d x %d fp64 cluster sums need %d bytes, more than the %d available; "
-                         "reduce k or the number of features" % (k, n, need, limit))
-    lab = _c(labels.to(device=dev, dtype=torch.int32))
-    counts = label_counts(lab, k)
-    if out is not None:
-        if out.shape != (k, n) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
-            raise ValueError("csr_cluster_sums: out must be a contiguous fp64 (%d, %d) tensor on %s" % (k, n, dev))
-        sums = zero_(out)
-    else:
-        sums = zeros((k, n), dtype=torch.float64, device=dev)
-    if m == 0 or b == a or k == 0 or n == 0:
-        return sums, counts
-    scale = 0.0
-    if deterministic():
-        scale = csr_fixed_scale(m, float(A.data[a:b].abs().max().item()) if vmax is None else float(vmax))
-    if not A.data.is_cuda:
-        rl = lab.long()[_csr_km_rows(A, a, b)]
-        ok = (rl >= 0) & (rl < k)
-        cell = rl[ok] * n + A.indices[a:b].long()[ok]
-        v = A.data[a:b].double()[ok]
-        if scale:
-            acc = torch.zeros(k * n, dtype=torch.int64).index_add_(0, cell, torch.round(v * scale).long())
-            sums.copy_((acc.double() * (1.0 / scale)).view(k, n))
-        else:
-            sums.view(-1).index_add_(0, cell, v)
-        return sums, counts
-    native.call("srml_csr_cluster_sums_" + _sfx(A), _c(A.indptr).data_ptr(), A.indices.data_ptr(), A.data.data_ptr(),
-                m, n, b - a, lab.data_ptr(), k, scale, sums.data_ptr(), native.stream(dev))
-    if scale:
-        native.call("srml_csr_cluster_sums_finish", sums.data_ptr(), k * n, 1.0 / scale, native.stream(dev))
-    return sums, counts
+    lab = _c(labels.to(device=A.data.device, dtype=torch.int32))
+    kernel = "srml_csr_cluster_sums_" + _sfx(A) if A.data.is_cuda else None
+    sums = _csr_label_sums("csr_cluster_sums", A, lab, k, None, vmax, out, kernel)
+    return sums, label_counts(lab, k)
 
 
 def csr_gather_dense(A: Any, rows: torch.Tensor) -> torch.Tensor:
@@ -5358,14 +5391,6 @@ def csr_silhouette_kp(k: int) -> int:
     return 8 if k <= 8 else 16 if k <= 16 else 32 if k <= 32 else (k + 63) // 64 * 64
 
 
-def _csr_sil_refused(name: str, rc: int, rows: int, k: int, kp: int) -> None:
-    if rc < 0:
-        raise ValueError("%s refused the launch (status %d: -1 grid overflow, -2 cluster count / padding) for %d "
-                         "rows, k=%d, kp=%d" % (name, rc, rows, k, kp))
-    if rc != 0:
-        raise RuntimeError("%s launch failed with HIP status %d" % (name, rc))
-
-
 def _sil_seg_sum(lab: torch.Tensor, k: int, v: Optional[torch.Tensor]) -> torch.Tensor:
     """fp64 [k] per-label sums of the per-row fp64 scalars ``v`` (None: ones). Device: the fixed-order
     segment fold of the dense path (``label_sort`` + ``srml_silhouette_seg_scalars``)."""
@@ -5398,11 +5423,10 @@ def _csr_sil_rows(A: Any, mu: Optional[torch.Tensor]) -> torch.Tensor:
         return torch.zeros(m, dtype=torch.float64, device=dev).index_add_(0, rows, (v - u) ** 2 - u * u) + mu2
     out = torch.empty(m, dtype=torch.float64, device=dev)
     indptr = _c(A.indptr)
-    for r0 in range(0, m, _CSR_KM_LAUNCH_ROWS):
-        r = min(_CSR_KM_LAUNCH_ROWS, m - r0)
+    for r0, r in _csr_row_chunks(m, csr_silhouette_config()[2]):
         rc = native.call_status("srml_csr_silhouette_rows_f32", indptr[r0:].data_ptr(), A.indices.data_ptr(),
                                 A.data.data_ptr(), r, native.ptr(mud), mu2, out[r0:].data_ptr(), native.stream(dev))
-        _csr_sil_refused("srml_csr_silhouette_rows_f32", rc, r, 0, 0)
+        _csr_refused("srml_csr_silhouette_rows_f32", "cluster", rc, r, 0, 0)
     return out
 
 
@@ -5420,20 +5444,11 @@ def _csr_sil_sums(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int, 
     factor f_i = w_i (cosine: w_i / ||x_i||). Device fp32 values: ``srml_csr_silhouette_sums_f32``, one
     fp64 atomic per non-zero, or in deterministic mode exact i64 fixed-point atomics scaled by
     ``csr_fixed_scale(m, max|f| max|value|)`` (a bound of max|f_i value|) that repeat bit for bit. N
-    is a fixed-order segment fold. A k x n buffer past ``_CSR_KM_SUMS_BYTES`` (or the device's free
-    memory) raises ``ValueError``."""
-    m, n = int(A.shape[0]), int(A.shape[1])
-    a, b = _csr_km_check(A)
-    dev = A.data.device
+    is a fixed-order segment fold. The rest is ``_csr_label_sums``."""
+    m = int(A.shape[0])
+    _csr_km_check(A)
     if lab.numel() != m or (w is not None and w.numel() != m):
         raise ValueError("silhouette_sums: labels / weights do not match the %d rows" % m)
-    need = k * n * 8
-    limit = _CSR_KM_SUMS_BYTES
-    if A.data.is_cuda and need <= limit:
-        limit = min(limit, int(torch.cuda.mem_get_info(dev)[0]))
-    if need > limit:
-        raise ValueError("silhouette_sums: the %d x %d fp64 cluster sums need %d bytes, more than the %d available; "
-                         "reduce k or the number of features" % (k, n, need, limit))
     lab = _c(lab.to(torch.int32))
     N = _sil_seg_sum(lab, k, w)
     f = w
@@ -5441,28 +5456,8 @@ def _csr_sil_sums(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int, 
         sq = _csr_sil_cos_norms(A, w)
         f = torch.where(sq > 0, sq.rsqrt(), torch.zeros_like(sq))
         f = f if w is None else f * w
-    Y = zeros((k, n), dtype=torch.float64, device=dev)
-    if m == 0 or b == a:
-        return N, Y
-    scale = 0.0
-    if deterministic():
-        scale = csr_fixed_scale(m, float(A.data[a:b].abs().max()) * (1.0 if f is None else float(f.max())))
-    if not _csr_sil_native(A):
-        rows = _csr_km_rows(A, a, b)
-        cell = lab.long()[rows] * n + A.indices[a:b].long()
-        v = A.data[a:b].double() if f is None else A.data[a:b].double() * f[rows]
-        if scale:
-            acc = torch.zeros(k * n, dtype=torch.int64, device=dev).index_add_(0, cell, torch.round(v * scale).long())
-            Y.copy_((acc.double() * (1.0 / scale)).view(k, n))
-        else:
-            Y.view(-1).index_add_(0, cell, v)
-        return N, Y
-    st = native.stream(dev)
-    native.call("srml_csr_silhouette_sums_f32", _c(A.indptr).data_ptr(), A.indices.data_ptr(), A.data.data_ptr(), m, n,
-                b - a, lab.data_ptr(), k, native.ptr(None if f is None else _c(f)), scale, Y.data_ptr(), st)
-    if scale:
-        native.call("srml_csr_cluster_sums_finish", Y.data_ptr(), k * n, 1.0 / scale, st)
-    return N, Y
+    kernel = "srml_csr_silhouette_sums_f32" if _csr_sil_native(A) else None
+    return N, _csr_label_sums("silhouette_sums", A, lab, k, f, None, None, kernel)
 
 
 def _csr_silhouette(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int, measure: str,
@@ -5496,12 +5491,7 @@ def _csr_silhouette(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int
     use_kernel = _csr_sil_native(A)
     kp = csr_silhouette_kp(k) if use_kernel else k
     if use_kernel:
-        need = n * kp * 4
-        limit = min(_CSR_KM_CT_BYTES, int(torch.cuda.mem_get_info(dev)[0]))
-        if need > limit:
-            raise ValueError("silhouette: the %d x %d transposed cluster table (k = %d padded to %d) needs %d bytes, "
-                             "more than the %d available; reduce k or the number of features"
-                             % (n, kp, k, kp, need, limit))
+        _csr_table_budget("silhouette", "cluster", n, kp, k, 4, dev)
     Nd = torch.where(live, N, torch.ones_like(N))
     sum_w = w.sum() if w is not None else torch.tensor(float(m), dtype=torch.float64, device=dev)
     mu = None if cos else silhouette_centre(N, Y).double()
@@ -5537,17 +5527,16 @@ def _csr_silhouette(A: Any, lab: torch.Tensor, w: Optional[torch.Tensor], k: int
     lab32, Nc, indptr, st = _c(lab.to(torch.int32)), _c(N.double()), _c(A.indptr), native.stream(dev)
     s = torch.empty(m, dtype=torch.float32, device=dev) if rows_out else None
     rpb = csr_silhouette_config()[2]
-    step = _CSR_KM_LAUNCH_ROWS // rpb * rpb
-    part = torch.empty((min(m, step) + rpb - 1) // rpb, dtype=torch.float64, device=dev)
-    outs = torch.empty((m + step - 1) // step, dtype=torch.float64, device=dev)
-    for i, r0 in enumerate(range(0, m, step)):
-        r = min(step, m - r0)
+    chunks = list(_csr_row_chunks(m, rpb))
+    part = torch.empty((chunks[0][1] + rpb - 1) // rpb, dtype=torch.float64, device=dev)  # the first is the longest
+    outs = torch.empty(len(chunks), dtype=torch.float64, device=dev)
+    for i, (r0, r) in enumerate(chunks):
         rc = native.call_status("srml_csr_silhouette_f32", indptr[r0:].data_ptr(), A.indices.data_ptr(),
                                 A.data.data_ptr(), r, MT.data_ptr(), k, kp, g.data_ptr(), tc.data_ptr(), Nc.data_ptr(),
                                 rv[r0:].data_ptr(), lab32[r0:].data_ptr(), None if w is None else w[r0:].data_ptr(),
                                 int(cos), None if s is None else s[r0:].data_ptr(), part.data_ptr(),
                                 outs[i:].data_ptr(), st)
-        _csr_sil_refused("srml_csr_silhouette_f32", rc, r, k, kp)
+        _csr_refused("srml_csr_silhouette_f32", "cluster", rc, r, k, kp)
     sws = outs[0]
     for i in range(1, outs.numel()):  # the launches in order
         sws = sws + outs[i]

@@ -8,69 +8,39 @@
 //    fp64 atomics or, for bit-reproducible results, exact i64 fixed-point integer atomics that
 //    srml_csr_cluster_sums_finish converts to fp64 in place.
 //
-// CSR layout as in csr_knn.hip: int64 row offsets, int32 column indices, ABSOLUTE offsets (a row
-// block is a pointer into the row offsets of the whole matrix). Column indices are in [0, n),
-// validated by the caller before any launch; the kernels do not check again.
+// The CSR layout, the one-wave-per-row table scheme with its constants and per-non-zero accumulate,
+// and the label-sums kernel behind srml_csr_cluster_sums are in csr_table.h.
 //
-// srml_csr_nearest: one wave per row, KM_ROWS waves per block. The centres come TRANSPOSED and
-// padded, CT[n][kp] with kp a multiple of 64 (padding columns zero, their |c|^2 = +inf). A non-zero
-// (col, val) of the row is wave-uniform; lane l accumulates centres tile + l + 64 s, s < KM_KS, so
-// one non-zero costs KM_KS reads of 64 consecutive values of CT row `col` (256 B each in fp32) and
-// KM_KS fused multiply-adds per lane: one accumulator chain per (lane, s), products added in column
-// order, no cross-lane sum and no atomics. k > KM_TK = 64 KM_KS loops over centre tiles; the row's
-// first KM_STAGE (col, val) pairs are staged once in LDS and re-used by every tile, a longer row
-// re-reads its tail from global memory. |x|^2 is summed in fp64 from the same values (lane-strided
-// partials, DPP reduction) and rounded once. Per tile each lane folds its KM_KS keys into a running
-// (min, arg-min) in ascending index order with a strict compare; a 6-step butterfly on (key, index)
-// picks the wave's minimum, the lower index on equal keys.
-#include "common.h"
+// srml_csr_nearest: the centres come TRANSPOSED and padded, CT[n][kp] with kp a multiple of 64
+// (padding columns zero, their |c|^2 = +inf). |x|^2 is summed in fp64 in the pass that stages the
+// row (lane-strided partials, DPP reduction) and rounded once. Per tile each lane folds its CSR_KS
+// keys into a running (min, arg-min) in ascending index order with a strict compare; a 6-step
+// butterfly on (key, index) picks the wave's minimum, the lower index on equal keys.
+#include "csr_table.h"
 
 namespace {
-constexpr int KM_ROWS = 4;             // rows (waves) per block
-constexpr int KM_T = 64 * KM_ROWS;     // threads per block
-constexpr int KM_KS = 4;               // accumulators per lane
-constexpr int KM_TK = 64 * KM_KS;      // centres per pass
-constexpr int KM_STAGE = 512;          // non-zeros of a row staged in LDS
-
 template <typename T>
-__device__ __forceinline__ T km_fma(T a, T b, T c);
-template <>
-__device__ __forceinline__ float km_fma<float>(float a, float b, float c) { return fmaf(a, b, c); }
-template <>
-__device__ __forceinline__ double km_fma<double>(double a, double b, double c) { return fma(a, b, c); }
-
-__device__ __forceinline__ float km_shfl_xor(float v, int o) { return __shfl_xor(v, o, 64); }
-__device__ __forceinline__ double km_shfl_xor(double v, int o) { return __shfl_xor(v, o, 64); }
-
-template <typename T>
-__device__ __forceinline__ void km_accumulate(const T* __restrict__ ct, T v, int tile, int kp, T (&acc)[KM_KS]) {
-#pragma unroll
-  for (int s = 0; s < KM_KS; ++s)
-    if (tile + 64 * s < kp) acc[s] = km_fma<T>(v, ct[64 * s], acc[s]);  // wave-uniform condition
-}
-
-template <typename T>
-__global__ __launch_bounds__(KM_T) void csr_nearest_kernel(const long* __restrict__ indptr,
-                                                           const int* __restrict__ indices,
-                                                           const T* __restrict__ data, long m,
-                                                           const T* __restrict__ CT, const T* __restrict__ cnorm,
-                                                           int k, int kp, int* __restrict__ labels,
-                                                           T* __restrict__ dist) {
-  __shared__ int sI[KM_ROWS][KM_STAGE];
-  __shared__ T sV[KM_ROWS][KM_STAGE];
+__global__ __launch_bounds__(CSR_T) void csr_nearest_kernel(const long* __restrict__ indptr,
+                                                            const int* __restrict__ indices,
+                                                            const T* __restrict__ data, long m,
+                                                            const T* __restrict__ CT, const T* __restrict__ cnorm,
+                                                            int k, int kp, int* __restrict__ labels,
+                                                            T* __restrict__ dist) {
+  __shared__ int sI[CSR_ROWS][CSR_STAGE];
+  __shared__ T sV[CSR_ROWS][CSR_STAGE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long r = (long)blockIdx.x * KM_ROWS + wave;
+  const long r = (long)blockIdx.x * CSR_ROWS + wave;
   long p0 = 0, nnz = 0;
   if (r < m) {
     p0 = indptr[r];
     nnz = indptr[r + 1] - p0;
   }
-  const int ns = nnz < KM_STAGE ? (int)nnz : KM_STAGE;
+  const int ns = nnz < CSR_STAGE ? (int)nnz : CSR_STAGE;
   double sq = 0.0;
   for (long p = lane; p < nnz; p += 64) {
     const T v = data[p0 + p];
     sq = fma((double)v, (double)v, sq);
-    if (p < KM_STAGE) {
+    if (p < CSR_STAGE) {
       sI[wave][p] = indices[p0 + p];
       sV[wave][p] = v;
     }
@@ -80,19 +50,19 @@ __global__ __launch_bounds__(KM_T) void csr_nearest_kernel(const long* __restric
   if (r >= m) return;
   T best = (T)__builtin_inff();
   int bi = 0x7fffffff;
-  for (int tile = 0; tile < kp; tile += KM_TK) {
-    T acc[KM_KS];
+  for (int tile = 0; tile < kp; tile += CSR_TK) {
+    T acc[CSR_KS];
 #pragma unroll
-    for (int s = 0; s < KM_KS; ++s) acc[s] = (T)0;
+    for (int s = 0; s < CSR_KS; ++s) acc[s] = (T)0;
     const T* ct = CT + tile + lane;
 #pragma unroll 4
-    for (int p = 0; p < ns; ++p) km_accumulate<T>(ct + (long)sI[wave][p] * kp, sV[wave][p], tile, kp, acc);
-    for (long p = KM_STAGE; p < nnz; ++p) km_accumulate<T>(ct + (long)indices[p0 + p] * kp, data[p0 + p], tile, kp, acc);
+    for (int p = 0; p < ns; ++p) csr_accumulate<T>(ct + (long)sI[wave][p] * kp, sV[wave][p], tile, kp, acc);
+    for (long p = CSR_STAGE; p < nnz; ++p) csr_accumulate<T>(ct + (long)indices[p0 + p] * kp, data[p0 + p], tile, kp, acc);
 #pragma unroll
-    for (int s = 0; s < KM_KS; ++s) {
+    for (int s = 0; s < CSR_KS; ++s) {
       const int j = tile + 64 * s + lane;
       if (j < k) {  // j < k <= kp: the padding never competes
-        const T key = km_fma<T>((T)-2, acc[s], xn + cnorm[j]);
+        const T key = csr_fma<T>((T)-2, acc[s], xn + cnorm[j]);
         const T d = key > (T)0 ? key : (T)0;
         if (d < best) {  // ascending j per lane: strict keeps the lower index
           best = d;
@@ -103,7 +73,7 @@ __global__ __launch_bounds__(KM_T) void csr_nearest_kernel(const long* __restric
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    const T ob = km_shfl_xor(best, o);
+    const T ob = csr_shfl_xor(best, o);
     const int oi = __shfl_xor(bi, o, 64);
     if (ob < best || (ob == best && oi < bi)) {
       best = ob;
@@ -113,32 +83,6 @@ __global__ __launch_bounds__(KM_T) void csr_nearest_kernel(const long* __restric
   if (lane == 0) {
     labels[r] = bi;
     dist[r] = best;
-  }
-}
-
-// A group of G lanes owns one row and strides its non-zeros. FIXED: the value is scaled by the
-// power of two `scale`, rounded to an integer and added with 64-bit integer atomics (wrap-around
-// two's complement: the caller's scale keeps every true sum inside i64).
-template <typename T, int G, bool FIXED>
-__global__ __launch_bounds__(256) void csr_cluster_sums_kernel(const long* __restrict__ indptr,
-                                                               const int* __restrict__ indices,
-                                                               const T* __restrict__ data, long m, int n,
-                                                               const int* __restrict__ labels, int k, double scale,
-                                                               double* __restrict__ sums) {
-  constexpr int GPB = 256 / G;
-  const int g = threadIdx.x / G, l = threadIdx.x % G;
-  for (long r = (long)blockIdx.x * GPB + g; r < m; r += (long)gridDim.x * GPB) {
-    const int lab = labels[r];
-    if ((unsigned)lab >= (unsigned)k) continue;  // never outside the buffer
-    double* row = sums + (long)lab * n;
-    const long p1 = indptr[r + 1];
-    for (long p = indptr[r] + l; p < p1; p += G) {
-      const double v = (double)data[p];
-      if constexpr (FIXED)
-        atomicAdd(reinterpret_cast<unsigned long long*>(row + indices[p]), (unsigned long long)__double2ll_rn(v * scale));
-      else
-        atomicAdd(row + indices[p], v);
-    }
   }
 }
 
@@ -186,38 +130,11 @@ int km_nearest(const long* indptr, const int* indices, const T* data, long m, co
                int kp, int* labels, T* dist, hipStream_t stream) {
   if (m <= 0) return 0;
   if (k <= 0 || kp < k || kp % 64 != 0) return -2;
-  const long blocks = (m + KM_ROWS - 1) / KM_ROWS;
-  if (blocks > srml_max_blocks(KM_T)) return -1;
-  hipLaunchKernelGGL((csr_nearest_kernel<T>), dim3((unsigned)blocks), dim3(KM_T), 0, stream, indptr, indices, data, m,
+  const long blocks = csr_row_blocks(m);
+  if (blocks < 0) return -1;
+  hipLaunchKernelGGL((csr_nearest_kernel<T>), dim3((unsigned)blocks), dim3(CSR_T), 0, stream, indptr, indices, data, m,
                      CT, cnorm, k, kp, labels, dist);
   return srml_status();
-}
-
-template <typename T, int G>
-int km_sums_g(const long* indptr, const int* indices, const T* data, long m, int n, const int* labels, int k,
-              double scale, double* sums, hipStream_t stream) {
-  constexpr int GPB = 256 / G;
-  long blocks = (m + GPB - 1) / GPB;
-  if (blocks > 256L * 64) blocks = 256L * 64;  // grid-stride beyond 64 blocks per CU
-  if (scale != 0.0)
-    hipLaunchKernelGGL((csr_cluster_sums_kernel<T, G, true>), dim3((unsigned)blocks), dim3(256), 0, stream, indptr,
-                       indices, data, m, n, labels, k, scale, sums);
-  else
-    hipLaunchKernelGGL((csr_cluster_sums_kernel<T, G, false>), dim3((unsigned)blocks), dim3(256), 0, stream, indptr,
-                       indices, data, m, n, labels, k, scale, sums);
-  return srml_status();
-}
-
-template <typename T>
-int km_sums(const long* indptr, const int* indices, const T* data, long m, int n, long nnz, const int* labels, int k,
-            double scale, double* sums, hipStream_t stream) {
-  if (m <= 0) return 0;
-  if (k <= 0 || n <= 0) return -2;
-  const long mean = nnz / m;
-  if (mean <= 12) return km_sums_g<T, 8>(indptr, indices, data, m, n, labels, k, scale, sums, stream);
-  if (mean <= 24) return km_sums_g<T, 16>(indptr, indices, data, m, n, labels, k, scale, sums, stream);
-  if (mean <= 48) return km_sums_g<T, 32>(indptr, indices, data, m, n, labels, k, scale, sums, stream);
-  return km_sums_g<T, 64>(indptr, indices, data, m, n, labels, k, scale, sums, stream);
 }
 }  // namespace
 
@@ -225,9 +142,9 @@ int km_sums(const long* indptr, const int* indices, const T* data, long m, int n
 // non-zeros per row, 2 rows per block.
 SRML_API int srml_csr_kmeans_config(int which) {
   switch (which) {
-    case 0: return KM_TK;
-    case 1: return KM_STAGE;
-    case 2: return KM_ROWS;
+    case 0: return CSR_TK;
+    case 1: return CSR_STAGE;
+    case 2: return CSR_ROWS;
     default: return -1;
   }
 }
@@ -260,13 +177,13 @@ SRML_API int srml_csr_centres_transpose_f64(const double* C, int k, int n, int k
 SRML_API int srml_csr_cluster_sums_f32(const long* indptr, const int* indices, const float* data, long m, int n,
                                        long nnz, const int* labels, int k, double scale, double* sums,
                                        hipStream_t stream) {
-  return km_sums<float>(indptr, indices, data, m, n, nnz, labels, k, scale, sums, stream);
+  return csr_label_sums<float>(indptr, indices, data, m, n, nnz, labels, k, nullptr, scale, sums, stream);
 }
 
 SRML_API int srml_csr_cluster_sums_f64(const long* indptr, const int* indices, const double* data, long m, int n,
                                        long nnz, const int* labels, int k, double scale, double* sums,
                                        hipStream_t stream) {
-  return km_sums<double>(indptr, indices, data, m, n, nnz, labels, k, scale, sums, stream);
+  return csr_label_sums<double>(indptr, indices, data, m, n, nnz, labels, k, nullptr, scale, sums, stream);
 }
 
 // buf[i] = (double)(i64 at buf[i]) * inv_scale, in place, i < count

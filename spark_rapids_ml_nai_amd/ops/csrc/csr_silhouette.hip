@@ -4,14 +4,15 @@
 // M_c = m_c - mu (fp32, stored transposed), g_c = mu . M_c and r_i = ||x_i - mu||^2,
 //   squaredEuclidean: d(i, c) = r_i + t_c - 2 (sum_{j in nz(i)} x_ij M_cj - g_c),  t_c = Psi'_c / N_c
 //   cosine:           d(i, c) = 1 - (sum_{j in nz(i)} x_ij m_cj) / ||x_i||          (mu = 0, t = g = 0)
-// so the only work per non-zero is a sparse dot against the table. CSR layout as in csr_kmeans.hip:
-// int64 ABSOLUTE row offsets, int32 column indices in [0, n), validated by the caller.
+// so the only work per non-zero is a sparse dot against the table. The CSR layout (int64 ABSOLUTE
+// row offsets, int32 column indices in [0, n), validated by the caller), the table scheme of the
+// kp > 64 kernel and the label-sums kernel are in csr_table.h, shared with csr_kmeans.hip.
 //
 //  * srml_csr_silhouette_rows_f32 — one wave per row: r_i = sum_nz (x - mu_j)^2 + (||mu||^2 - sum_nz
 //    mu_j^2), or ||x_i||^2 without mu, lane-strided fp64 partials folded in a fixed order.
 //  * srml_csr_silhouette_sums_f32 — Y[label][col] += f_i value (f_i = w_i, times 1 / ||x_i|| under
-//    cosine): fp64 atomics, or exact i64 fixed-point atomics (srml_csr_cluster_sums_finish converts).
-//  * srml_csr_silhouette_f32 — the scoring kernel. One wave owns a row, CS_ROWS waves a block. The
+//    cosine): csr_table.h's label sums with the per-row factor.
+//  * srml_csr_silhouette_f32 — the scoring kernel. One wave owns a row, CSR_ROWS waves a block. The
 //    table is MT[n][kp] fp32, kp = k rounded up to 8, 16, 32 or a multiple of 64, padding zero and
 //    t = +inf there (as for an empty cluster).
 //    kp <= 64 (KP = kp): lane = (e, c), c = lane % KP, e = lane / KP. The wave keeps E = 64 / KP
@@ -19,31 +20,24 @@
 //      KP consecutive floats of MT[col] (32 .. 256 B contiguous), one FMA per lane, CS_U such reads
 //      outstanding per lane. After the row the E partial dots of a cluster are folded with log2(E)
 //      xor steps at strides KP, 2 KP, ...: a fixed order.
-//    kp > 64: tiles of 64 CS_KS clusters, CS_KS accumulators per lane, the row's first CS_STAGE
-//      (col, val) pairs staged once in LDS and re-used by every tile, a longer row re-reads its
-//      tail from global memory (the scheme of csr_nearest_kernel).
+//    kp > 64: tiles of CSR_TK clusters on the row staged in LDS, the table scheme of csr_table.h.
 //    Epilogue in registers, fp64: lane c forms d_c and routes it by label == c into the own-cluster
 //    value or the running minimum over the other non-empty clusters (across tiles); a butterfly
 //    takes the minimum; N / (N - w), the singleton rule and the three-way formula give s (fp32).
 //    w s goes to a fixed-order fp64 block slot, a second kernel adds the slots in block order: no
 //    atomics, bit-identical run to run for given summaries.
-#include "common.h"
+#include "csr_table.h"
 
 namespace {
-constexpr int CS_ROWS = 4;             // rows (waves) per block
-constexpr int CS_T = 64 * CS_ROWS;     // threads per block
-constexpr int CS_U = 4;                // table reads in flight per lane (kp <= 64)
-constexpr int CS_KS = 4;               // accumulators per lane (kp > 64)
-constexpr int CS_TK = 64 * CS_KS;      // clusters per tile (kp > 64)
-constexpr int CS_STAGE = 512;          // non-zeros of a row staged in LDS (kp > 64)
+constexpr int CS_U = 4;  // table reads in flight per lane (kp <= 64)
 
-__global__ __launch_bounds__(CS_T) void csr_sil_rows_kernel(const long* __restrict__ indptr,
-                                                            const int* __restrict__ indices,
-                                                            const float* __restrict__ data, long m,
-                                                            const double* __restrict__ mu, double mu2,
-                                                            double* __restrict__ out) {
+__global__ __launch_bounds__(CSR_T) void csr_sil_rows_kernel(const long* __restrict__ indptr,
+                                                             const int* __restrict__ indices,
+                                                             const float* __restrict__ data, long m,
+                                                             const double* __restrict__ mu, double mu2,
+                                                             double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * CS_ROWS + (threadIdx.x >> 6);
+  const long r = (long)blockIdx.x * CSR_ROWS + (threadIdx.x >> 6);
   if (r >= m) return;  // wave-uniform
   const long p1 = indptr[r + 1];
   double a = 0.0, b = 0.0;
@@ -60,35 +54,6 @@ __global__ __launch_bounds__(CS_T) void csr_sil_rows_kernel(const long* __restri
   a = wave_sum(a);
   if (mu) a += mu2 - wave_sum(b);  // the columns the row does not touch: ||mu||^2 less the touched ones
   if (lane == 0) out[r] = a;
-}
-
-// A group of G lanes owns one row and strides its non-zeros (csr_cluster_sums_kernel with a per-row
-// factor). FIXED: f value is scaled by the power of two `scale`, rounded to an integer and added
-// with 64-bit integer atomics, exact in any order.
-template <int G, bool FIXED>
-__global__ __launch_bounds__(256) void csr_sil_sums_kernel(const long* __restrict__ indptr,
-                                                           const int* __restrict__ indices,
-                                                           const float* __restrict__ data, long m, int n,
-                                                           const int* __restrict__ labels, int k,
-                                                           const double* __restrict__ f, double scale,
-                                                           double* __restrict__ sums) {
-  constexpr int GPB = 256 / G;
-  const int g = threadIdx.x / G, l = threadIdx.x % G;
-  for (long r = (long)blockIdx.x * GPB + g; r < m; r += (long)gridDim.x * GPB) {
-    const int lab = labels[r];
-    if ((unsigned)lab >= (unsigned)k) continue;  // never outside the buffer
-    const double fi = f ? f[r] : 1.0;
-    if (fi == 0.0) continue;
-    double* row = sums + (long)lab * n;
-    const long p1 = indptr[r + 1];
-    for (long p = indptr[r] + l; p < p1; p += G) {
-      const double v = fi * (double)data[p];
-      if constexpr (FIXED)
-        atomicAdd(reinterpret_cast<unsigned long long*>(row + indices[p]), (unsigned long long)__double2ll_rn(v * scale));
-      else
-        atomicAdd(row + indices[p], v);
-    }
-  }
 }
 
 // What the epilogue needs besides the dot: per cluster g, t (+inf: empty or padding) and N, per row
@@ -148,29 +113,29 @@ __device__ __forceinline__ double sil_finish(const SilEpi& ep, const SilRow& sr,
   return wi * (double)s;
 }
 
-// the block's slot: its CS_ROWS rows in wave order
+// the block's slot: its CSR_ROWS rows in wave order
 __device__ __forceinline__ void sil_block_slot(double wsv, double* __restrict__ part) {
-  __shared__ double ws_s[CS_ROWS];
+  __shared__ double ws_s[CSR_ROWS];
   if ((threadIdx.x & 63) == 0) ws_s[threadIdx.x >> 6] = wsv;
   __syncthreads();
   if (threadIdx.x == 0) {
     double t = ws_s[0];
 #pragma unroll
-    for (int i = 1; i < CS_ROWS; ++i) t += ws_s[i];
+    for (int i = 1; i < CSR_ROWS; ++i) t += ws_s[i];
     part[blockIdx.x] = t;
   }
 }
 
 template <int KP>
-__global__ __launch_bounds__(CS_T) void csr_sil_small_kernel(const long* __restrict__ indptr,
-                                                             const int* __restrict__ indices,
-                                                             const float* __restrict__ data, long m,
-                                                             const float* __restrict__ MT, SilEpi ep,
-                                                             float* __restrict__ s_out, double* __restrict__ part) {
+__global__ __launch_bounds__(CSR_T) void csr_sil_small_kernel(const long* __restrict__ indptr,
+                                                              const int* __restrict__ indices,
+                                                              const float* __restrict__ data, long m,
+                                                              const float* __restrict__ MT, SilEpi ep,
+                                                              float* __restrict__ s_out, double* __restrict__ part) {
   constexpr int E = 64 / KP;
   const int lane = threadIdx.x & 63;
   const int c = lane % KP, e = lane / KP;
-  const long row = (long)blockIdx.x * CS_ROWS + (threadIdx.x >> 6);
+  const long row = (long)blockIdx.x * CSR_ROWS + (threadIdx.x >> 6);
   const double inf = (double)__builtin_inff();
   double wsv = 0.0;
   if (row < m) {  // wave-uniform
@@ -200,29 +165,22 @@ __global__ __launch_bounds__(CS_T) void csr_sil_small_kernel(const long* __restr
   sil_block_slot(wsv, part);
 }
 
-__device__ __forceinline__ void sil_accumulate(const float* __restrict__ ct, float v, int tile, int kp,
-                                               float (&acc)[CS_KS]) {
-#pragma unroll
-  for (int s = 0; s < CS_KS; ++s)
-    if (tile + 64 * s < kp) acc[s] = fmaf(v, ct[64 * s], acc[s]);  // wave-uniform condition
-}
-
-__global__ __launch_bounds__(CS_T) void csr_sil_wide_kernel(const long* __restrict__ indptr,
-                                                            const int* __restrict__ indices,
-                                                            const float* __restrict__ data, long m,
-                                                            const float* __restrict__ MT, int kp, SilEpi ep,
-                                                            float* __restrict__ s_out, double* __restrict__ part) {
-  __shared__ int sI[CS_ROWS][CS_STAGE];
-  __shared__ float sV[CS_ROWS][CS_STAGE];
+__global__ __launch_bounds__(CSR_T) void csr_sil_wide_kernel(const long* __restrict__ indptr,
+                                                             const int* __restrict__ indices,
+                                                             const float* __restrict__ data, long m,
+                                                             const float* __restrict__ MT, int kp, SilEpi ep,
+                                                             float* __restrict__ s_out, double* __restrict__ part) {
+  __shared__ int sI[CSR_ROWS][CSR_STAGE];
+  __shared__ float sV[CSR_ROWS][CSR_STAGE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long row = (long)blockIdx.x * CS_ROWS + wave;
+  const long row = (long)blockIdx.x * CSR_ROWS + wave;
   const double inf = (double)__builtin_inff();
   long p0 = 0, nnz = 0;
   if (row < m) {
     p0 = indptr[row];
     nnz = indptr[row + 1] - p0;
   }
-  const int ns = nnz < CS_STAGE ? (int)nnz : CS_STAGE;
+  const int ns = nnz < CSR_STAGE ? (int)nnz : CSR_STAGE;
   for (int p = lane; p < ns; p += 64) {
     sI[wave][p] = indices[p0 + p];
     sV[wave][p] = data[p0 + p];
@@ -232,16 +190,17 @@ __global__ __launch_bounds__(CS_T) void csr_sil_wide_kernel(const long* __restri
   if (row < m) {
     const SilRow sr = sil_row(ep, row);
     double own = inf, oth = inf;
-    for (int tile = 0; tile < kp; tile += CS_TK) {
-      float acc[CS_KS];
+    for (int tile = 0; tile < kp; tile += CSR_TK) {
+      float acc[CSR_KS];
 #pragma unroll
-      for (int s = 0; s < CS_KS; ++s) acc[s] = 0.f;
+      for (int s = 0; s < CSR_KS; ++s) acc[s] = 0.f;
       const float* ct = MT + tile + lane;
 #pragma unroll 4
-      for (int p = 0; p < ns; ++p) sil_accumulate(ct + (long)sI[wave][p] * kp, sV[wave][p], tile, kp, acc);
-      for (long p = CS_STAGE; p < nnz; ++p) sil_accumulate(ct + (long)indices[p0 + p] * kp, data[p0 + p], tile, kp, acc);
+      for (int p = 0; p < ns; ++p) csr_accumulate<float>(ct + (long)sI[wave][p] * kp, sV[wave][p], tile, kp, acc);
+      for (long p = CSR_STAGE; p < nnz; ++p)
+        csr_accumulate<float>(ct + (long)indices[p0 + p] * kp, data[p0 + p], tile, kp, acc);
 #pragma unroll
-      for (int s = 0; s < CS_KS; ++s)
+      for (int s = 0; s < CSR_KS; ++s)
         if (tile + 64 * s < kp) sil_route(ep, sr, acc[s], tile + 64 * s + lane, own, oth);
     }
     wsv = sil_finish(ep, sr, own, oth, row, s_out);
@@ -265,36 +224,22 @@ __global__ __launch_bounds__(256) void csr_sil_fold_kernel(const double* __restr
   if (threadIdx.x == 0) out[0] = s_s[0];
 }
 
-template <int G>
-int sil_sums_g(const long* indptr, const int* indices, const float* data, long m, int n, const int* labels, int k,
-               const double* f, double scale, double* sums, hipStream_t stream) {
-  constexpr int GPB = 256 / G;
-  long blocks = (m + GPB - 1) / GPB;
-  if (blocks > 256L * 64) blocks = 256L * 64;  // grid-stride beyond 64 blocks per CU
-  if (scale != 0.0)
-    hipLaunchKernelGGL((csr_sil_sums_kernel<G, true>), dim3((unsigned)blocks), dim3(256), 0, stream, indptr, indices,
-                       data, m, n, labels, k, f, scale, sums);
-  else
-    hipLaunchKernelGGL((csr_sil_sums_kernel<G, false>), dim3((unsigned)blocks), dim3(256), 0, stream, indptr, indices,
-                       data, m, n, labels, k, f, scale, sums);
-  return srml_status();
-}
-
 template <int KP>
 void sil_small(unsigned blocks, const long* indptr, const int* indices, const float* data, long m, const float* MT,
                const SilEpi& ep, float* s_out, double* part, hipStream_t stream) {
-  hipLaunchKernelGGL((csr_sil_small_kernel<KP>), dim3(blocks), dim3(CS_T), 0, stream, indptr, indices, data, m, MT, ep,
+  hipLaunchKernelGGL((csr_sil_small_kernel<KP>), dim3(blocks), dim3(CSR_T), 0, stream, indptr, indices, data, m, MT, ep,
                      s_out, part);
 }
 }  // namespace
 
 // The dispatch constants of this file, for the Python layer and the tests: 0 clusters per tile
-// (kp > 64), 1 staged non-zeros per row, 2 rows per block, 3 table reads in flight per lane.
+// (kp > 64), 1 staged non-zeros per row, 2 rows per block (csr_table.h's, as srml_csr_kmeans_config
+// returns them), 3 table reads in flight per lane.
 SRML_API int srml_csr_silhouette_config(int which) {
   switch (which) {
-    case 0: return CS_TK;
-    case 1: return CS_STAGE;
-    case 2: return CS_ROWS;
+    case 0: return CSR_TK;
+    case 1: return CSR_STAGE;
+    case 2: return CSR_ROWS;
     case 3: return CS_U;
     default: return -1;
   }
@@ -305,9 +250,9 @@ SRML_API int srml_csr_silhouette_config(int which) {
 SRML_API int srml_csr_silhouette_rows_f32(const long* indptr, const int* indices, const float* data, long m,
                                           const double* mu, double mu2, double* out, hipStream_t stream) {
   if (m <= 0) return 0;
-  const long blocks = (m + CS_ROWS - 1) / CS_ROWS;
-  if (blocks > srml_max_blocks(CS_T)) return -1;
-  hipLaunchKernelGGL(csr_sil_rows_kernel, dim3((unsigned)blocks), dim3(CS_T), 0, stream, indptr, indices, data, m, mu,
+  const long blocks = csr_row_blocks(m);
+  if (blocks < 0) return -1;
+  hipLaunchKernelGGL(csr_sil_rows_kernel, dim3((unsigned)blocks), dim3(CSR_T), 0, stream, indptr, indices, data, m, mu,
                      mu2, out);
   return srml_status();
 }
@@ -318,18 +263,12 @@ SRML_API int srml_csr_silhouette_rows_f32(const long* indptr, const int* indices
 SRML_API int srml_csr_silhouette_sums_f32(const long* indptr, const int* indices, const float* data, long m, int n,
                                           long nnz, const int* labels, int k, const double* f, double scale,
                                           double* sums, hipStream_t stream) {
-  if (m <= 0) return 0;
-  if (k <= 0 || n <= 0) return -2;
-  const long mean = nnz / m;
-  if (mean <= 12) return sil_sums_g<8>(indptr, indices, data, m, n, labels, k, f, scale, sums, stream);
-  if (mean <= 24) return sil_sums_g<16>(indptr, indices, data, m, n, labels, k, f, scale, sums, stream);
-  if (mean <= 48) return sil_sums_g<32>(indptr, indices, data, m, n, labels, k, f, scale, sums, stream);
-  return sil_sums_g<64>(indptr, indices, data, m, n, labels, k, f, scale, sums, stream);
+  return csr_label_sums<float>(indptr, indices, data, m, n, nnz, labels, k, f, scale, sums, stream);
 }
 
 // out[0] = sum_r w_r s_r over the m rows whose offsets start at indptr. MT: n x kp fp32; g, tc: kp
 // fp64 (tc = +inf for an empty cluster and for the padding); Nc: k fp64; rv, labels, w (null: 1),
-// s_out (null: not stored): m values; part: ceil(m / CS_ROWS) fp64 block slots.
+// s_out (null: not stored): m values; part: ceil(m / CSR_ROWS) fp64 block slots.
 // -1: the grid overflows, -2: k, kp inconsistent.
 SRML_API int srml_csr_silhouette_f32(const long* indptr, const int* indices, const float* data, long m, const float* MT,
                                      int k, int kp, const double* g, const double* tc, const double* Nc,
@@ -337,8 +276,8 @@ SRML_API int srml_csr_silhouette_f32(const long* indptr, const int* indices, con
                                      double* part, double* out, hipStream_t stream) {
   if (m <= 0) return 0;
   if (k <= 0 || kp < k || !(kp == 8 || kp == 16 || kp == 32 || kp % 64 == 0)) return -2;
-  const long nb = (m + CS_ROWS - 1) / CS_ROWS;
-  if (nb > srml_max_blocks(CS_T)) return -1;
+  const long nb = csr_row_blocks(m);
+  if (nb < 0) return -1;
   const SilEpi ep{g, tc, Nc, rv, labels, w, k, cosine};
   const unsigned blocks = (unsigned)nb;
   switch (kp) {
@@ -347,7 +286,7 @@ SRML_API int srml_csr_silhouette_f32(const long* indptr, const int* indices, con
     case 32: sil_small<32>(blocks, indptr, indices, data, m, MT, ep, s_out, part, stream); break;
     case 64: sil_small<64>(blocks, indptr, indices, data, m, MT, ep, s_out, part, stream); break;
     default:
-      hipLaunchKernelGGL(csr_sil_wide_kernel, dim3(blocks), dim3(CS_T), 0, stream, indptr, indices, data, m, MT, kp, ep,
+      hipLaunchKernelGGL(csr_sil_wide_kernel, dim3(blocks), dim3(CSR_T), 0, stream, indptr, indices, data, m, MT, kp, ep,
                          s_out, part);
   }
   int st = srml_status();

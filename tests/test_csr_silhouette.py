@@ -17,6 +17,7 @@ from spark_rapids_ml_nai_amd import ops
 from spark_rapids_ml_nai_amd.core.base import CSR
 from spark_rapids_ml_nai_amd.core.dataframe import DataFrame
 from spark_rapids_ml_nai_amd.evaluation import ClusteringEvaluator
+from spark_rapids_ml_nai_amd.utils.determinism import set_deterministic
 from test_silhouette import oracle
 
 U = 2.0 ** -24
@@ -180,3 +181,20 @@ def test_errors_before_any_work(monkeypatch):
     monkeypatch.setattr(ops, "_CSR_KM_SUMS_BYTES", 64)
     with pytest.raises(ValueError, match="cluster sums need"):
         ops.silhouette(to_csr(A, "cpu"), labt, 2)
+
+
+def sums_pair(device, weighted=False):
+    """(Y of ``silhouette_sums``, the sums of ``csr_cluster_sums``) of one case in deterministic mode."""
+    A, lab, w = make_case(129, 9, 100, weighted=weighted)
+    Ad, labd = to_csr(A, device), torch.from_numpy(lab).to(device)
+    set_deterministic(True)
+    try:
+        Y = ops.silhouette_sums(Ad, labd, 9, None if w is None else torch.from_numpy(w).to(device))[1]
+        return Y, ops.csr_cluster_sums(Ad, labd, 9)[0]
+    finally:
+        set_deterministic(None)
+
+
+def test_sums_without_a_factor_are_the_cluster_sums():
+    Y, sums = sums_pair("cpu")
+    assert torch.equal(Y, sums)  # one routine, exact integer sums on one scale

@@ -8,7 +8,7 @@ from spark_rapids_ml_nai_amd import ops
 from spark_rapids_ml_nai_amd.core.dataframe import DataFrame
 from spark_rapids_ml_nai_amd.evaluation import ClusteringEvaluator
 from spark_rapids_ml_nai_amd.utils.determinism import set_deterministic
-from test_csr_silhouette import bounds, check, lattice, make_case, to_csr
+from test_csr_silhouette import bounds, check, lattice, make_case, sums_pair, to_csr
 
 pytestmark = pytest.mark.gpu
 M = 129  # not a multiple of the rows per block
@@ -89,3 +89,14 @@ def test_evaluator_and_errors(monkeypatch):
     monkeypatch.setattr(ops, "_CSR_KM_CT_BYTES", 1024)
     with pytest.raises(ValueError, match="cluster table"):
         ops.silhouette(Ad, labd, 9, stats=stats)
+
+
+def test_config_is_the_shared_table_config():
+    km = ops.native.lib().srml_csr_kmeans_config
+    assert ops.csr_silhouette_config()[:3] == tuple(int(km(i)) for i in range(3))
+
+
+def test_sums_share_the_label_sums_kernel():
+    Y, sums = sums_pair("cuda")
+    assert torch.equal(Y, sums)  # no factor: the cluster sums, exact integer sums on one scale
+    assert torch.equal(sums_pair("cuda", weighted=True)[0].cpu(), sums_pair("cpu", weighted=True)[0])  # a factor
